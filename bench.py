@@ -10,8 +10,12 @@ rank runs its own ciphertexts (images are independent in the reference), the rel
 generated on rank 0 and broadcast over RCCL/xGMI once at setup; no collective in the data
 path -> weak scaling.
 
-Prints one JSON line (rank 0).  The cpu_baseline leg times the repo's CPU restatement of the
-reference algorithm (oracle/, "port") on the host cores of the same box.
+Prints one JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the
+headline figure (HMult/s, ms_per_step); --dump-outputs DIR also writes the last timed step's outputs
+as DIR/<name>.npy.  Everything else is behind --full: the oracle check of the timed outputs, the
+key-switch kernels' own times and rooflines, the ResNet legs, and the cpu_baseline leg, which times
+the repo's CPU restatement of the reference algorithm (oracle/, "port") on the host cores of the
+same box.
 """
 import argparse
 import glob
@@ -535,6 +539,34 @@ def check_timed_outputs(w, entries, threads):
             "vs": "oracle/mhe_oracle.c hmult (SEAL evaluator restatement), SEAL-layout key", "oracle_s": round(dt, 2)}
 
 
+DUMP_WORDS = 1 << 22  # residues --dump-outputs samples: 32 MiB as float64
+
+
+def dump_sample_index(total):
+    """Flat positions --dump-outputs keeps of an output of `total` words: all of them up to DUMP_WORDS,
+    else DUMP_WORDS sorted positions drawn with a fixed seed (None = all)."""
+    if total <= DUMP_WORDS:
+        return None
+    return np.sort(np.random.default_rng(20261019).integers(0, total, size=DUMP_WORDS, dtype=np.int64))
+
+
+def dump_outputs(w, directory, rank=0, world=1):
+    """--dump-outputs: what the timed path's last step left in its output buffers, the `batch` result
+    ciphertexts ([batch][2][L-1][n] residues, 1.4 GB at the default shape).  A fixed, seeded sample of
+    DUMP_WORDS flat positions (sorted; the whole output when it is smaller) is written as float64:
+    every residue is below its prime < 2^52, so the conversion is exact.  The inputs are seeded
+    (HMultWorkload), so two builds run with the same arguments can be compared word for word."""
+    os.makedirs(directory, exist_ok=True)
+    flat = w.out.reshape(-1)
+    idx = dump_sample_index(flat.numel())
+    if idx is not None:
+        flat = flat.index_select(0, torch.from_numpy(idx).to(flat.device))
+    name = "hmult_out" if world == 1 else f"hmult_out_rank{rank}"
+    path = os.path.join(directory, name + ".npy")
+    np.save(path, flat.cpu().numpy().astype(np.float64))
+    return path
+
+
 def launch_ranks(args):
     """`--gpus N` without a launcher: start N worker processes of this script (one per GPU, RANK /
     LOCAL_RANK / WORLD_SIZE / MASTER_* set) and exit with the first failing child's code.  This
@@ -613,6 +645,13 @@ def main():
     ap.add_argument("--streams", type=int, default=4,
                     help="HIP streams the batch is spread over (round robin; 4 = the hardware queues per process)")
     ap.add_argument("--stub", action="store_true", help="rank plumbing only, on gloo without a GPU (tests)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the oracle check of the timed outputs, the "
+                         "per-kernel times and rooflines (a single-stream pass of their own), the ResNet legs and the "
+                         "CPU baseline; the --no-cpu, --resnet-*, --c4 and --cpu-threads options act only with it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (a fixed seeded sample of the "
+                         "output ciphertexts' residues, float64) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -632,19 +671,18 @@ def main():
     torch.cuda.set_device(dev)
 
     L = args.limbs
-    check = rank == 0 and not args.no_cpu  # keep the SEAL-layout key on the host for the output check
+    full = args.full
+    # --full, rank 0: keep the SEAL-layout key on the host for the output check
+    check = full and rank == 0 and not args.no_cpu
     w = HMultWorkload(dev, rank, L, args.batch, args.hmult_group, args.streams, args.key_format, keep_host=check)
-    eng, n, moduli, B, G = w.eng, w.n, w.moduli, w.B, w.G
-    stream, sps = w.stream, w.sps
-    lib = mhe.lib()
-    lib.mhe_ctx_set_timing(eng._h, 1)
+    eng, moduli, B, G, stream = w.eng, w.moduli, w.B, w.G, w.stream
+    if full:  # the engine records HIP events around its key-switch kernels; read after the timed region
+        mhe.lib().mhe_ctx_set_timing(eng._h, 1)
     for _ in range(args.warmup):
         w.step()
     torch.cuda.synchronize(dev)
-    km_ms, km_n = mhe.ctypes.c_double(), mhe.ctypes.c_int()
-    mc_ms, mc_n = mhe.ctypes.c_double(), mhe.ctypes.c_int()  # k_modup_col, the second key-switch kernel
-    lib.mhe_kernel_time(eng._h, 0, mhe.ctypes.byref(km_ms), mhe.ctypes.byref(km_n))  # drop the warmup launches
-    lib.mhe_kernel_time(eng._h, 1, mhe.ctypes.byref(mc_ms), mhe.ctypes.byref(mc_n))
+    if full:
+        kernel_times(eng)  # drop the warmup launches
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize(dev)
@@ -662,66 +700,10 @@ def main():
     torch.cuda.synchronize(dev)
     gpu_s = ev0.elapsed_time(ev1) / 1e3
     elapsed = max_over_ranks(max(wall, gpu_s), dev)
-    # the timed calls' outputs, checked against the oracle on rank 0 (one entry per call, so every
-    # stream and batch position class is covered), before the single-stream pass below rewrites them
-    timed_check = None
-    if check:
-        entries = sorted({i0 + (ci * 3) % cnt for ci, (i0, cnt, _) in enumerate(w.call_streams())})
-        timed_check = check_timed_outputs(w, entries, args.cpu_threads)
-    # HIP-event time of the dominant kernel, recorded by the engine on the stream each launch
-    # ran on (mhe_ctx_set_timing / mhe_kernel_time).  With several streams the launches of
-    # different HMults overlap, so the kernel's own duration is taken from a short
-    # single-stream pass after the timed region (the rocprofv3 summary under profiles/ is of
-    # the same single-stream command: bench.py --streams 1).
-    lib.mhe_kernel_time(eng._h, 0, mhe.ctypes.byref(km_ms), mhe.ctypes.byref(km_n))
-    lib.mhe_kernel_time(eng._h, 1, mhe.ctypes.byref(mc_ms), mhe.ctypes.byref(mc_n))
-    if len(sps) > 1:
-        for _ in range(min(args.steps, 4)):
-            w.run_calls(sps[:1])
-        torch.cuda.synchronize(dev)
-        lib.mhe_kernel_time(eng._h, 0, mhe.ctypes.byref(km_ms), mhe.ctypes.byref(km_n))
-        lib.mhe_kernel_time(eng._h, 1, mhe.ctypes.byref(mc_ms), mhe.ctypes.byref(mc_n))
-    km_avg_us = km_ms.value * 1e3 / max(km_n.value, 1)
-    mc_avg_us = mc_ms.value * 1e3 / max(mc_n.value, 1)
-
-    # HBM traffic per HMult from the committed PMC passes of the same workload (rocprofv3
-    # FETCH_SIZE/WRITE_SIZE, gfx950-corrected; scripts/gpu_round.sh + scripts/traffic.py)
-    traffic, traffic_src, km_traffic = None, None, None
-    for f in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_traffic.json"))):
-        try:
-            t = json.load(open(f))
-            if t.get("limbs", L) == L:
-                traffic, traffic_src = t["hbm_bytes_per_hmult"], os.path.relpath(f, ROOT)
-                pk = {k.split("<")[0]: v for k, v in t.get("per_kernel_GB_per_hmult", {}).items()}
-                km_traffic = pk.get("k_ks_row_mac")
-                km_traffic = None if km_traffic is None else km_traffic * 1e9 * min(G, B)  # G HMults per launch
-        except (OSError, ValueError, KeyError):
-            pass
-
-    # SQ counters of the same workload (rocprofv3 --pmc SQ_INSTS_VALU ..., scripts/gpu_pmc.sh)
-    sq_valu, sq_src = None, None
-    for f in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_sq_counters.json"))):
-        try:
-            t = json.load(open(f))
-            if t.get("limbs", L) == L and "k_ks_row_mac" in t.get("SQ_INSTS_VALU", {}):
-                sq_valu, sq_src = t["SQ_INSTS_VALU"]["k_ks_row_mac"], os.path.relpath(f, ROOT)
-        except (OSError, ValueError, KeyError):
-            pass
-
+    if args.dump_outputs:  # the last timed step's outputs, before anything below runs on the buffers again
+        dump_outputs(w, args.dump_outputs, rank, world)
     hmults_per_gpu = B * args.steps
     value = world * hmults_per_gpu / elapsed
-    per_hmult_s = gpu_s / hmults_per_gpu  # HIP-event time per HMult (batch over its streams)
-    # algorithmic bytes as SURVEY.md §8(d) defines them (SEAL's u64 key layout); a prepared key
-    # streams fewer (streamed_key_bytes_per_launch), which is what the format buys
-    # one launch covers G HMults (mhe_hmult_batch): the key slice once, and every entry's target
-    # limbs read ([L][n]) and key inner products written ([2][L+1][n])
-    G_launch = min(G, B)
-    io_bytes = G_launch * (L + 2 * (L + 1)) * n * 8
-    km_bytes = ks_row_mac_key_bytes(L, n) + io_bytes
-    km_streamed = ks_row_mac_key_bytes(L, n, moduli, w.prepared) + io_bytes
-    hm_bytes = hmult_bytes(L)
-    achieved = hm_bytes / per_hmult_s / 1e9
-    km_achieved = km_bytes / (km_avg_us * 1e-6) / 1e9 if km_avg_us > 0 else 0.0
     result = {
         "metric": "homomorphic ciphertext mults/sec (N=2^16, L limbs)",
         "value": round(value, 3),
@@ -747,6 +729,119 @@ def main():
             "ranks": (dist.get_world_size() if world > 1 else 1),
             "backend": (dist.get_backend() if world > 1 else None),
         },
+    }
+    if full:
+        result.update(hmult_full_figures(args, w, dev, gpu_s, check))
+    # the HMult leg's engine (its per-stream workspaces: 8 entries at 44 limbs each) and buffers are
+    # not needed by the ResNet legs: destroyed here, not left to the garbage collector
+    torch.cuda.synchronize(dev)
+    w.eng.close()
+    del w
+    torch.cuda.empty_cache()
+    legs = []
+    if full and args.resnet_images > 0:
+        legs.append((args.resnet_layers, args.resnet_images, args.resnet_streams, args.resnet_fibers))
+    if full and (args.c4 == "on" or (args.c4 == "auto" and world > 1)):
+        legs.append((110, 1, 1, 1))  # config C4: ResNet-110, one image per GPU, shared key set
+    for layers, images, streams, fibers in legs:
+        r = resnet_leg(local, images, streams, layers, fibers, seed=args.resnet_seed,
+                       key_draws=args.resnet_key_draws if layers == 20 and world == 1 else 0)
+        t = torch.tensor([r["batch_wall_s"], r["sec_per_image_1stream"]], dtype=torch.float64, device=dev)
+        if world > 1:
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        r["batch_wall_s"], r["sec_per_image_1stream"] = float(t[0]), float(t[1])
+        r["images_per_s"] = round(world * images / r["batch_wall_s"], 4)
+        r["n_gpus"] = world
+        if layers == 20:
+            r["vs_reference_cpu"] = round(RESNET20_CPU_S / r["sec_per_image_1stream"], 1)
+        result[f"resnet{layers}"] = r
+    if full and rank == 0 and world == 1 and not args.no_cpu:
+        result["cpu_baseline"] = cpu_baseline(moduli, L, args.cpu_threads)
+        for layers in (20, 110):
+            r = result.get(f"resnet{layers}")
+            if r and r.get("ops_per_image"):
+                est = resnet_cpu_estimate(r["ops_per_image"], result["cpu_baseline"]["cores"])
+                est["vs_gpu_1stream"] = round(est["estimated_cpu_s_per_image"] / r["sec_per_image_1stream"], 1)
+                r["cpu_estimate"] = est
+    if rank == 0:
+        print(json.dumps(result), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def kernel_times(eng):
+    """((ms, launches) of k_ks_row_mac, (ms, launches) of k_modup_col, the second key-switch kernel):
+    what the engine's HIP events recorded since the last read (mhe_kernel_time; a read starts over)."""
+    out = []
+    for kind in (0, 1):
+        ms, cnt = mhe.ctypes.c_double(), mhe.ctypes.c_int()
+        mhe.lib().mhe_kernel_time(eng._h, kind, mhe.ctypes.byref(ms), mhe.ctypes.byref(cnt))
+        out.append((ms.value, cnt.value))
+    return out
+
+
+def hmult_full_figures(args, w, dev, gpu_s, check):
+    """--full: what the HMult leg reports beyond its headline figure, taken after the timed region on
+    the same workload -- the oracle check of the timed outputs (rank 0), the key-switch kernels' own
+    times (a single-stream pass) and the rooflines built on them."""
+    eng, n, moduli, B, G, L, sps = w.eng, w.n, w.moduli, w.B, w.G, w.L, w.sps
+    # the timed calls' outputs, checked against the oracle on rank 0 (one entry per call, so every
+    # stream and batch position class is covered), before the single-stream pass below rewrites them
+    timed_check = None
+    if check:
+        entries = sorted({i0 + (ci * 3) % cnt for ci, (i0, cnt, _) in enumerate(w.call_streams())})
+        timed_check = check_timed_outputs(w, entries, args.cpu_threads)
+    # HIP-event time of the dominant kernel, recorded by the engine on the stream each launch
+    # ran on (mhe_ctx_set_timing / mhe_kernel_time).  With several streams the launches of
+    # different HMults overlap, so the kernel's own duration is taken from a short
+    # single-stream pass after the timed region (the rocprofv3 summary under profiles/ is of
+    # the same single-stream command: bench.py --streams 1).
+    (km_ms, km_n), (mc_ms, mc_n) = kernel_times(eng)
+    if len(sps) > 1:
+        for _ in range(min(args.steps, 4)):
+            w.run_calls(sps[:1])
+        torch.cuda.synchronize(dev)
+        (km_ms, km_n), (mc_ms, mc_n) = kernel_times(eng)
+    km_avg_us = km_ms * 1e3 / max(km_n, 1)
+    mc_avg_us = mc_ms * 1e3 / max(mc_n, 1)
+
+    # HBM traffic per HMult from the committed PMC passes of the same workload (rocprofv3
+    # FETCH_SIZE/WRITE_SIZE, gfx950-corrected; scripts/gpu_round.sh + scripts/traffic.py)
+    traffic, traffic_src, km_traffic = None, None, None
+    for f in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_traffic.json"))):
+        try:
+            t = json.load(open(f))
+            if t.get("limbs", L) == L:
+                traffic, traffic_src = t["hbm_bytes_per_hmult"], os.path.relpath(f, ROOT)
+                pk = {k.split("<")[0]: v for k, v in t.get("per_kernel_GB_per_hmult", {}).items()}
+                km_traffic = pk.get("k_ks_row_mac")
+                km_traffic = None if km_traffic is None else km_traffic * 1e9 * min(G, B)  # G HMults per launch
+        except (OSError, ValueError, KeyError):
+            pass
+
+    # SQ counters of the same workload (rocprofv3 --pmc SQ_INSTS_VALU ..., scripts/gpu_pmc.sh)
+    sq_valu, sq_src = None, None
+    for f in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_sq_counters.json"))):
+        try:
+            t = json.load(open(f))
+            if t.get("limbs", L) == L and "k_ks_row_mac" in t.get("SQ_INSTS_VALU", {}):
+                sq_valu, sq_src = t["SQ_INSTS_VALU"]["k_ks_row_mac"], os.path.relpath(f, ROOT)
+        except (OSError, ValueError, KeyError):
+            pass
+
+    per_hmult_s = gpu_s / (B * args.steps)  # HIP-event time per HMult (batch over its streams)
+    # algorithmic bytes as SURVEY.md §8(d) defines them (SEAL's u64 key layout); a prepared key
+    # streams fewer (streamed_key_bytes_per_launch), which is what the format buys
+    # one launch covers G HMults (mhe_hmult_batch): the key slice once, and every entry's target
+    # limbs read ([L][n]) and key inner products written ([2][L+1][n])
+    G_launch = min(G, B)
+    io_bytes = G_launch * (L + 2 * (L + 1)) * n * 8
+    km_bytes = ks_row_mac_key_bytes(L, n) + io_bytes
+    km_streamed = ks_row_mac_key_bytes(L, n, moduli, w.prepared) + io_bytes
+    hm_bytes = hmult_bytes(L)
+    achieved = hm_bytes / per_hmult_s / 1e9
+    km_achieved = km_bytes / (km_avg_us * 1e-6) / 1e9 if km_avg_us > 0 else 0.0
+    return {
         # rank 0 recomputed entries of the timed calls (the last step's outputs, one entry per
         # mhe_hmult_batch call / stream) with the oracle on the same inputs: identical words
         "timed_output_checked": timed_check is not None,
@@ -769,7 +864,7 @@ def main():
             "streamed_key_bytes_per_launch": km_streamed,
             "avg_launch_us": round(km_avg_us, 2),
             "modup_col_avg_launch_us": round(mc_avg_us, 2),
-            "launches_timed": km_n.value,
+            "launches_timed": km_n,
             "timing": "HIP events around each launch on its stream; single-stream pass when --streams > 1",
             # with one key stream shared by G_launch HMults the kernel moves few bytes per HMult and is
             # bound by FP64 VALU issue instead: valu_roofline (model lane-ops; SQ_INSTS_VALU when
@@ -807,41 +902,6 @@ def main():
             "us_per_hmult": round(per_hmult_s * 1e6, 2),
         },
     }
-    # the HMult leg's engine (its per-stream workspaces: 8 entries at 44 limbs each) and buffers are
-    # not needed by the ResNet legs: destroyed here, not left to the garbage collector
-    torch.cuda.synchronize(dev)
-    w.eng.close()
-    del w
-    torch.cuda.empty_cache()
-    legs = []
-    if args.resnet_images > 0:
-        legs.append((args.resnet_layers, args.resnet_images, args.resnet_streams, args.resnet_fibers))
-    if args.c4 == "on" or (args.c4 == "auto" and world > 1):
-        legs.append((110, 1, 1, 1))  # config C4: ResNet-110, one image per GPU, shared key set
-    for layers, images, streams, fibers in legs:
-        r = resnet_leg(local, images, streams, layers, fibers, seed=args.resnet_seed,
-                       key_draws=args.resnet_key_draws if layers == 20 and world == 1 else 0)
-        t = torch.tensor([r["batch_wall_s"], r["sec_per_image_1stream"]], dtype=torch.float64, device=dev)
-        if world > 1:
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        r["batch_wall_s"], r["sec_per_image_1stream"] = float(t[0]), float(t[1])
-        r["images_per_s"] = round(world * images / r["batch_wall_s"], 4)
-        r["n_gpus"] = world
-        if layers == 20:
-            r["vs_reference_cpu"] = round(RESNET20_CPU_S / r["sec_per_image_1stream"], 1)
-        result[f"resnet{layers}"] = r
-    if rank == 0 and world == 1 and not args.no_cpu:
-        result["cpu_baseline"] = cpu_baseline(moduli, L, args.cpu_threads)
-        for layers in (20, 110):
-            r = result.get(f"resnet{layers}")
-            if r and r.get("ops_per_image"):
-                est = resnet_cpu_estimate(r["ops_per_image"], result["cpu_baseline"]["cores"])
-                est["vs_gpu_1stream"] = round(est["estimated_cpu_s_per_image"] / r["sec_per_image_1stream"], 1)
-                r["cpu_estimate"] = est
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

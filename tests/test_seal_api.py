@@ -175,8 +175,9 @@ def test_resnet110_end_to_end():
 def test_resnet110_params_fixture():
     """The lossless 4-byte ".d7" packing of ResNet-110's parameters: the C++ loader
     (load_resnet_params_bin) and the Python decoder of make_resnet_params.py agree value for value
-    (count and left-to-right sum printed by `resnet_test ... -1 110`, no GPU); where the reference
-    is mounted, the decoded values equal the reference's text parsed as doubles."""
+    (count and left-to-right sum printed by `resnet_test ... -1 110`, no GPU), and the decoded
+    values equal the reference's text parsed as doubles (its first convolution's weights and the
+    final layer's biases, stored in tests/golden/resnet/resnet110_params_sample.json)."""
     import numpy as np
 
     sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
@@ -192,12 +193,12 @@ def test_resnet110_params_fixture():
                        capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     assert f"params: {v.size} values, sum {sum(v.tolist())!r}" in r.stdout, r.stdout
-    src = "/root/reference/pretrained_parameters/resnet110_new"
-    if os.path.isdir(src):
-        w = np.array([float(t) for t in open(os.path.join(src, "conv1_weight.txt")).read().split()[:432]])
-        assert np.array_equal(v[:432], w)
-        b = np.array([float(t) for t in open(os.path.join(src, "linear_bias.txt")).read().split()[:10]])
-        assert np.array_equal(v[-10:], b)
+    import json
+
+    ref = json.load(open(os.path.join(ROOT, "tests", "golden", "resnet", "resnet110_params_sample.json")))
+    assert len(ref["conv1_weight"]) == 432 and len(ref["linear_bias"]) == 10
+    assert np.array_equal(v[:432], np.array(ref["conv1_weight"]))
+    assert np.array_equal(v[-10:], np.array(ref["linear_bias"]))
 
 
 @pytest.mark.gpu
