@@ -199,9 +199,7 @@ struct HoistShared
     int key_limbs[MHE_HOIST_R];
     int Z; // items (<= MHE_MAXB)
 };
-#ifndef MHE_HOIST_PF
-#define MHE_HOIST_PF 2 // digits of key / D words in flight ahead of the one being staged
-#endif
+constexpr int MHE_HOIST_PF = 2; // digits of key / D words in flight ahead of the one being staged
 template <int R>
 __global__ __launch_bounds__(1024) void k_ks_hoist_mac_sh(HoistShared P, const PrimeDev *__restrict__ primes,
                                                           const TwF *__restrict__ cm, int L, int K, int log_n)

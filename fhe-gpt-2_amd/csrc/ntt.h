@@ -373,9 +373,6 @@ __global__ __launch_bounds__(256) void k_fwd_col(Job job, int log_n, long long t
 // butterflies, and hands them to store(x, v, pre).  Without it each store's loads wait for the
 // previous store (the compiler cannot move a load above a store that may alias it): E serialised
 // HBM round trips per lane at the end of the kernel.
-#ifndef MHE_ROW_PRE
-#define MHE_ROW_PRE 1
-#endif
 template <class V, class = void>
 struct PreOf
 {
@@ -386,7 +383,7 @@ template <class V>
 struct PreOf<V, std::void_t<typename V::Pre>>
 {
     using type = typename V::Pre;
-    static constexpr bool value = MHE_ROW_PRE != 0;
+    static constexpr bool value = true;
 };
 
 // A View with `static constexpr bool brev = true` stores position x of each 256-slot block from slot
@@ -413,17 +410,14 @@ __device__ __forceinline__ u32 brev8_ntt(u32 x)
 // (SQ_LDS_BANK_CONFLICT 6.5x the LDS busy cycles, profiles/r03k).  XOR-ing the low LOGE bits with
 // the high ones and a row pitch of R + TPS words makes both patterns conflict-free for every row
 // shape (bank model of MI355X_MICROARCH.md §LDS: 64 banks, 32-lane groups for ds_*_b64).
-#ifndef MHE_ROW_SWZ
-#define MHE_ROW_SWZ 1
-#endif
 template <int LOGR, int LOGT>
 struct RowLds
 {
     static constexpr int R = 1 << LOGR, TPS = 1 << LOGT, LOGE = LOGR - LOGT, E = 1 << LOGE;
-    static constexpr int LD = MHE_ROW_SWZ ? R + TPS : R + 1;
+    static constexpr int LD = R + TPS;
     __device__ static __forceinline__ int at(int sl, int p)
     {
-        return sl * LD + (MHE_ROW_SWZ ? (p ^ ((p >> LOGE) & (E - 1))) : p);
+        return sl * LD + (p ^ ((p >> LOGE) & (E - 1)));
     }
 };
 
@@ -440,15 +434,8 @@ __device__ __forceinline__ u32 lay(u32 t, int e, int b_lo)
     return ((t >> b_lo) << (b_lo + 3)) | ((u32)e << b_lo) | (t & ((1u << b_lo) - 1));
 }
 
-// Row passes load the twiddles of the first stage(s) after their transpose together with the data
-// (MHE_ROW_TWPF=0: where the stage uses them)
-#ifndef MHE_ROW_TWPF
-#define MHE_ROW_TWPF 1
-#endif
-// row passes at n = 2^16 in FP64 run k_fwd_row3 / k_inv_row3 (8 residues per lane, three phases)
-#ifndef MHE_ROW3
-#define MHE_ROW3 1
-#endif
+// Row passes load the twiddles of the first stage(s) after their transpose together with the data.
+// Row passes at n = 2^16 in FP64 run k_fwd_row3 / k_inv_row3 (8 residues per lane, three phases).
 
 // --------------------------------------------------------------------- forward, row pass
 // FP with the up-front prefetch: 3 waves/SIMD (<= 168 VGPRs)
@@ -485,14 +472,11 @@ __global__ __launch_bounds__(256, (FP && PRE_ON) ? 3 : 1) void k_fwd_row(Job job
     // s >= LOGE uses entries (rb << s) + (E t >> (LOGR - s)) + (e >> (LOGR - s)).
     using TWT = typename A::TW;
     constexpr int C0 = E >> (LOGR - LOGE), C1 = E >> (LOGR - LOGE - 1);
-    [[maybe_unused]] TWT p0[C0], p1[C1];
-    if constexpr (MHE_ROW_TWPF)
-    {
+    TWT p0[C0], p1[C1];
 #pragma unroll
-        for (int j = 0; j < C0; j++) p0[j] = ar.tw[(rb << LOGE) + ((E * t) >> (LOGR - LOGE)) + j];
+    for (int j = 0; j < C0; j++) p0[j] = ar.tw[(rb << LOGE) + ((E * t) >> (LOGR - LOGE)) + j];
 #pragma unroll
-        for (int j = 0; j < C1; j++) p1[j] = ar.tw[(rb << (LOGE + 1)) + ((E * t) >> (LOGR - LOGE - 1)) + j];
-    }
+    for (int j = 0; j < C1; j++) p1[j] = ar.tw[(rb << (LOGE + 1)) + ((E * t) >> (LOGR - LOGE - 1)) + j];
 #pragma unroll
     for (int s = 0; s < LOGE; s++)
         ar.template fwd<E>(v, 1 << (LOGE - 1 - s), [&](int e) { return (rb << s) + (e >> (LOGE - s)); });
@@ -504,9 +488,9 @@ __global__ __launch_bounds__(256, (FP && PRE_ON) ? 3 : 1) void k_fwd_row(Job job
 #pragma unroll
     for (int s = LOGE; s < LOGR; s++)
     {
-        if (MHE_ROW_TWPF && s == LOGE)
+        if (s == LOGE)
             ar.template fwd_tab<E>(v, 1 << (LOGR - 1 - s), p0, [&](int e) { return e >> (LOGR - s); });
-        else if (MHE_ROW_TWPF && s == LOGE + 1)
+        else if (s == LOGE + 1)
             ar.template fwd_tab<E>(v, 1 << (LOGR - 1 - s), p1, [&](int e) { return e >> (LOGR - s); });
         else
             ar.template fwd<E>(v, 1 << (LOGR - 1 - s), [&](int e) { return (rb << s) + ((E * t + e) >> (LOGR - s)); });
@@ -563,9 +547,6 @@ __global__ __launch_bounds__(256, (FP && PRE_ON) ? 3 : 1) void k_fwd_row(Job job
 // The twiddles of stage s of a 2^8-point row in layout lay(t, e, b_lo) (b_lo + s <= 8): entry
 // (rb << s) + (hi >> (8 - s)) + (e >> (8 - s - b_lo)), hi the lane's bits above the layout's e
 // bits -- 2^(b_lo + s - 5) distinct values (at least 1), loaded ahead of the stage's turn.
-#ifndef MHE_ROW3_PF
-#define MHE_ROW3_PF 1
-#endif
 template <int S_, int BLO, class AR>
 __device__ __forceinline__ void row3_tw(const AR &ar, u32 rb, u32 t, typename AR::TW (&w)[4])
 {
@@ -623,30 +604,19 @@ __global__ __launch_bounds__(256) void k_fwd_row3(Job job, int log_n, long long 
 #pragma unroll
         for (int e = 0; e < 8; e++) v[e] = x[swz(lay(t, e, to))];
     };
-    if constexpr (MHE_ROW3_PF)
-    {
-        // the first stage of each later phase takes twiddles loaded a phase ahead: the transposes'
-        // fences would otherwise hold their loads back to the stage itself
-        using TWT = typename A::TW;
-        TWT w3[4], w6[4];
-        row3_tw<3, B_B>(ar, rb, t, w3);
-        stages(B_A, 0, 3);
-        row3_tw<6, 0>(ar, rb, t, w6);
-        transpose(B_A, B_B);
-        ar.template fwd_tab<8>(v, 1 << (LOGR - 1 - 3 - B_B), w3, [&](int e) { return e >> (8 - 3 - B_B); });
-        stages(B_B, 4, 6);
-        transpose(B_B, 0);
-        ar.template fwd_tab<8>(v, 1 << (LOGR - 1 - 6), w6, [&](int e) { return e >> (8 - 6); });
-        stages(0, 7, 8);
-    }
-    else
-    {
-        stages(B_A, 0, 3);
-        transpose(B_A, B_B);
-        stages(B_B, 3, 6);
-        transpose(B_B, 0);
-        stages(0, 6, 8);
-    }
+    // the first stage of each later phase takes twiddles loaded a phase ahead: the transposes'
+    // fences would otherwise hold their loads back to the stage itself
+    using TWT = typename A::TW;
+    TWT w3[4], w6[4];
+    row3_tw<3, B_B>(ar, rb, t, w3);
+    stages(B_A, 0, 3);
+    row3_tw<6, 0>(ar, rb, t, w6);
+    transpose(B_A, B_B);
+    ar.template fwd_tab<8>(v, 1 << (LOGR - 1 - 3 - B_B), w3, [&](int e) { return e >> (8 - 3 - B_B); });
+    stages(B_B, 4, 6);
+    transpose(B_B, 0);
+    ar.template fwd_tab<8>(v, 1 << (LOGR - 1 - 6), w6, [&](int e) { return e >> (8 - 6); });
+    stages(0, 7, 8);
     // back to the coalesced layout for the epilogue; a brev View (hoist.h) stores at position p the
     // value of position brev8(p)
     wave_lds_fence();
@@ -690,12 +660,9 @@ __global__ __launch_bounds__(256) void k_inv_row(Job job, int log_n, long long t
     T v[E];
     // the first stage's twiddles with the data (see k_fwd_row): entries (rb << s) + (E t >> 1) + j
     using TWT = typename A::TW;
-    [[maybe_unused]] TWT p0[E / 2];
-    if constexpr (MHE_ROW_TWPF)
-    {
+    TWT p0[E / 2];
 #pragma unroll
-        for (int j = 0; j < E / 2; j++) p0[j] = ar.tw[(rb << (LOGR - 1)) + ((E * t) >> 1) + j];
-    }
+    for (int j = 0; j < E / 2; j++) p0[j] = ar.tw[(rb << (LOGR - 1)) + ((E * t) >> 1) + j];
 #pragma unroll
     for (int e = 0; e < E; e++) lds[RL::at(sl, t + TPS * e)] = ar.in(V.load(base + t + TPS * e));
     wave_lds_fence(); // a sub-transform is TPS <= 16 consecutive lanes of one wave
@@ -704,7 +671,7 @@ __global__ __launch_bounds__(256) void k_inv_row(Job job, int log_n, long long t
 #pragma unroll
     for (int s = LOGR - 1; s >= LOGE; s--)
     {
-        if (MHE_ROW_TWPF && s == LOGR - 1)
+        if (s == LOGR - 1)
             ar.template inv_tab<E>(v, 1 << (LOGR - 1 - s), p0, [&](int e) { return e >> 1; });
         else
             ar.template inv<E>(v, 1 << (LOGR - 1 - s), [&](int e) { return (rb << s) + ((E * t + e) >> (LOGR - s)); });
@@ -755,33 +722,22 @@ __global__ __launch_bounds__(256) void k_inv_row3(Job job, int log_n, long long 
 #pragma unroll
         for (int e = 0; e < 8; e++) v[e] = x[swz(lay(t, e, to))];
     };
-    if constexpr (MHE_ROW3_PF)
-    {
-        using TWT = typename A::TW;
-        TWT w7[4], w6[4], w5[4], w2[4];
-        row3_tw<7, 0>(ar, rb, t, w7);
-        row3_tw<6, 0>(ar, rb, t, w6);
-        transpose(B_A, 0); // loaded coalesced
-        row3_tw<5, B_B>(ar, rb, t, w5);
-        ar.template inv_tab<8>(v, 1 << (LOGR - 1 - 7), w7, [&](int e) { return e >> (8 - 7); });
-        ar.template inv_tab<8>(v, 1 << (LOGR - 1 - 6), w6, [&](int e) { return e >> (8 - 6); });
-        transpose(0, B_B);
-        row3_tw<2, B_A>(ar, rb, t, w2);
-        ar.template inv_tab<8>(v, 1 << (LOGR - 1 - 5 - B_B), w5, [&](int e) { return e >> (8 - 5 - B_B); });
-        stages(B_B, 4, 3);
-        transpose(B_B, B_A);
-        ar.template inv_tab<8>(v, 1 << (LOGR - 1 - 2 - B_A), w2, [&](int e) { return e >> (8 - 2 - B_A); });
-        stages(B_A, 1, 0);
-    }
-    else
-    {
-        transpose(B_A, 0); // loaded coalesced
-        stages(0, 7, 6);
-        transpose(0, B_B);
-        stages(B_B, 5, 3);
-        transpose(B_B, B_A);
-        stages(B_A, 2, 0);
-    }
+    // twiddles a phase ahead, as in k_fwd_row3
+    using TWT = typename A::TW;
+    TWT w7[4], w6[4], w5[4], w2[4];
+    row3_tw<7, 0>(ar, rb, t, w7);
+    row3_tw<6, 0>(ar, rb, t, w6);
+    transpose(B_A, 0); // loaded coalesced
+    row3_tw<5, B_B>(ar, rb, t, w5);
+    ar.template inv_tab<8>(v, 1 << (LOGR - 1 - 7), w7, [&](int e) { return e >> (8 - 7); });
+    ar.template inv_tab<8>(v, 1 << (LOGR - 1 - 6), w6, [&](int e) { return e >> (8 - 6); });
+    transpose(0, B_B);
+    row3_tw<2, B_A>(ar, rb, t, w2);
+    ar.template inv_tab<8>(v, 1 << (LOGR - 1 - 5 - B_B), w5, [&](int e) { return e >> (8 - 5 - B_B); });
+    stages(B_B, 4, 3);
+    transpose(B_B, B_A);
+    ar.template inv_tab<8>(v, 1 << (LOGR - 1 - 2 - B_A), w2, [&](int e) { return e >> (8 - 2 - B_A); });
+    stages(B_A, 1, 0);
 #pragma unroll
     for (int e = 0; e < 8; e++) V.store(base + lay(t, e, B_A), ar.out(v[e]));
 }
@@ -834,11 +790,8 @@ __global__ __launch_bounds__(256) void k_inv_col(Job job, int log_n, long long t
 // round trip disappear, and the outputs are the same words.
 // The first register phase of a forward column pass (stages 0 .. LOGE-1) uses twiddle entries
 // 1 .. E-1, the same for every lane: read them as scalar loads of the prime's FP table (ftab), issued
-// together, instead of per-stage LDS reads each waited for a few instructions later.
-#ifndef MHE_COL_STW
-#define MHE_COL_STW 0 // k_icol_lift / k_col_lift2 (FP): scalar first-phase twiddles (k_modup_col: MHE_MODUP_STW);
-                      // measured equal (profiles/r06s), so off
-#endif
+// together, instead of per-stage LDS reads each waited for a few instructions later.  k_modup_col's FP
+// sweeps only: in k_icol_lift / k_col_lift2 it measured equal (profiles/r06s).
 template <int E, int LOGE, class AR>
 __device__ __forceinline__ void fwd_first_phase_s(const AR &ar, typename AR::T (&v)[E], const void *ftab)
 {
@@ -880,10 +833,9 @@ struct ColSrc
     }
 };
 
-#ifndef MHE_ICOL_G
-#define MHE_ICOL_G 5 // at most this many output primes per lift-pass workgroup (icol_lift_a); 5 fills the LDS
-                     // of 3 workgroups per CU: 8 rescales at 25 limbs -5 % against 3 (profiles/r06w)
-#endif
+// at most this many output primes per lift-pass workgroup (icol_lift_a); 5 fills the LDS of 3 workgroups
+// per CU: 8 rescales at 25 limbs -5 % against 3 (profiles/r06w)
+constexpr int MHE_ICOL_G = 5;
 template <int LOGR, int LOGT, class Job, bool FP>
 __global__ __launch_bounds__(256, 3) void k_icol_lift(ColSrc cs, Job job, int cnt, int log_n, long long dinv,
                                                       long long dfwd)
@@ -966,14 +918,9 @@ __global__ __launch_bounds__(256, 3) void k_icol_lift(ColSrc cs, Job job, int cn
                 T v[E];
 #pragma unroll
                 for (int e = 0; e < E; e++) v[e] = fp_reduce(cd[e], ar.q, ar.qinv);
-                if constexpr (MHE_COL_STW)
-                    fwd_first_phase_s<E, LOGE>(ar, v, reinterpret_cast<const char *>(V.tw) + dfwd);
-                else
-                {
 #pragma unroll
-                    for (int st = 0; st < LOGE; st++)
-                        ar.template fwd_tab<E>(v, 1 << (LOGE - 1 - st), tl, [&](int e) { return (1 << st) + (e >> (LOGE - st)); });
-                }
+                for (int st = 0; st < LOGE; st++)
+                    ar.template fwd_tab<E>(v, 1 << (LOGE - 1 - st), tl, [&](int e) { return (1 << st) + (e >> (LOGE - st)); });
                 lds_barrier(); // lds still holds the previous prime's (or the inverse pass's) transpose
 #pragma unroll
                 for (int e = 0; e < E; e++) lds[sl * LD + t + TPS * e] = v[e];
@@ -1064,14 +1011,9 @@ __global__ __launch_bounds__(256, 3) void k_col_lift2(Job job, int cnt, int log_
             T v[E];
 #pragma unroll
             for (int e = 0; e < E; e++) v[e] = fp_reduce(V.lift_f(ca[e], cb[e]), ar.q, ar.qinv);
-            if constexpr (MHE_COL_STW)
-                fwd_first_phase_s<E, LOGE>(ar, v, reinterpret_cast<const char *>(V.tw) + dfwd);
-            else
-            {
 #pragma unroll
-                for (int st = 0; st < LOGE; st++)
-                    ar.template fwd_tab<E>(v, 1 << (LOGE - 1 - st), tl, [&](int e) { return (1 << st) + (e >> (LOGE - st)); });
-            }
+            for (int st = 0; st < LOGE; st++)
+                ar.template fwd_tab<E>(v, 1 << (LOGE - 1 - st), tl, [&](int e) { return (1 << st) + (e >> (LOGE - st)); });
             lds_barrier(); // lds still holds the previous prime's transpose
 #pragma unroll
             for (int e = 0; e < E; e++) lds[sl * LD + t + TPS * e] = v[e];
@@ -1109,32 +1051,12 @@ struct KsPtrs
     const int *run_if[MHE_MAXB]; // non-null: the entry's workgroups return unless *run_if != 0 (hoist.h fallback)
 };
 
-#ifndef MHE_MODUP_OCC
-#define MHE_MODUP_OCC 3 // waves per SIMD the ModUp column pass is compiled for (168 VGPRs)
-#endif
-#ifndef MHE_MODUP_WAVE
-#define MHE_MODUP_WAVE 0 // n = 2^16: a column's lanes in one wave, wave-local transposes (k_modup_col);
-                         // with non-temporal stores 8x slower (16-byte store segments, profiles/r06f)
-#endif
-#ifndef MHE_MODUP_PING
-#define MHE_MODUP_PING 1 // n = 2^16: alternate two LDS images per output prime, one barrier per prime (k_modup_col)
-#endif
-#ifndef MHE_MODUP_STW
-#define MHE_MODUP_STW 1 // k_modup_col (FP): first-phase twiddles as scalar loads instead of LDS reads
-#endif
-#ifndef MHE_MODUP_TPF
-#define MHE_MODUP_TPF 0 // k_modup_col: stage-4 (2: and stage-5) twiddles read before the transpose; at 168 VGPRs
-                        // both spill (6 / 14 bytes per lane), so off
-#endif
-#ifndef MHE_MODUP_TWG
-#define MHE_MODUP_TWG 5 // output primes per group whose twiddles the ModUp column pass stages in LDS
-#endif
+constexpr int MHE_MODUP_OCC = 3; // waves per SIMD the ModUp column pass is compiled for (168 VGPRs)
+constexpr int MHE_MODUP_TWG = 5; // output primes per group whose twiddles the ModUp column pass stages in LDS
 // MIX (with FP): output primes >= 2^51 (the GPT-2 chain's special prime) take the integer sweep.
 // The integer and MIX variants get 2 waves/SIMD: at 3 (168 VGPRs) they spilled 116-124 bytes per
 // lane, and each scratch reload waits for every store in flight (one vmcnt for loads and stores)
-#ifndef MHE_MODUP_OCC_INT
-#define MHE_MODUP_OCC_INT 2
-#endif
+constexpr int MHE_MODUP_OCC_INT = 2;
 template <int LOGR, int LOGT, bool FP, bool MIX = false>
 __global__ __launch_bounds__(256, (FP && !MIX) ? MHE_MODUP_OCC : MHE_MODUP_OCC_INT) void k_modup_col(KsPtrs P, const PrimeDev *__restrict__ primes,
                                                    const Tw *__restrict__ tw_all, int L, int K, int log_n,
@@ -1148,15 +1070,8 @@ __global__ __launch_bounds__(256, (FP && !MIX) ? MHE_MODUP_OCC : MHE_MODUP_OCC_I
     using T = typename A::T;
     constexpr int E = SH::E, TPS = SH::TPS, LOGE = SH::LOGE, S = SH::S, LD = SH::LD;
     constexpr int R = SH::R;
-    // MHE_MODUP_WAVE (n = 2^16, 16 lanes per column): a column's 16 lanes are consecutive lanes of
-    // one wave (4 columns per wave) instead of one lane in each of 16 waves' worth of rows, so the
-    // transpose between the two register phases stays inside the wave: no workgroup barrier per
-    // output prime (round 5: two, a third of the kernel's wave time waiting).  The column's LDS image
-    // is unpadded and XOR-skewed (wslot): conflict-free for the transpose's ds_write_b64 (one column's
-    // 16 lanes) and ds_read_b64 (two columns' 32 lanes) under MI355X_MICROARCH.md §LDS's bank rules.
-    constexpr bool WV = MHE_MODUP_WAVE && LOGR == 8 && TPS == 16;
-    // MHE_MODUP_PING (n = 2^16): the transpose's LDS image alternates between two placements from
-    // one output prime to the next.  Prime k writes row t + 16e of its column at the slot the same
+    // PG (n = 2^16, 16 lanes per column): the transpose's LDS image alternates between two placements
+    // from one output prime to the next.  Prime k writes row t + 16e of its column at the slot the same
     // lane read row 16t + e from in prime k - 1, and reads row 16t + e from the slot it wrote row
     // t + 16e to in prime k - 1: every slot a lane overwrites was last read by that lane itself, so
     // the barrier after each prime's reads (round 5: two barriers per prime) is not needed.  The
@@ -1166,21 +1081,14 @@ __global__ __launch_bounds__(256, (FP && !MIX) ? MHE_MODUP_OCC : MHE_MODUP_OCC_I
     // (MI355X_MICROARCH.md §LDS): the writes are conflict-free either way (16 lanes, sl = 0..15); the
     // reads of rows 16t + e from the swapped placement (element sl * 257 + t + 16e) are 2-way
     // conflicted, on every second output prime.
-    constexpr bool PG = !WV && MHE_MODUP_PING && LOGR == 8 && TPS == 16;
-#ifndef MHE_MODUP_LDS_EXTRA
-#define MHE_MODUP_LDS_EXTRA 0 // A/B only: extra elements in the LDS image (occupancy probe)
-#endif
-#ifndef MHE_MODUP_PING_BAR
-#define MHE_MODUP_PING_BAR 0 // A/B only: keep the end-of-prime barrier with the ping-pong image
-#endif
-    __shared__ T lds[(WV ? S * R : S * LD) + MHE_MODUP_LDS_EXTRA];
-    auto wslot = [](int col, int r) { return col * R + ((r ^ ((r >> 4) & 15)) ^ ((col & 1) << 4)); };
+    constexpr bool PG = LOGR == 8 && TPS == 16;
+    __shared__ T lds[S * LD];
     // The column-pass twiddles of the group's output primes (entries 1 .. R-1 of each prime's table,
     // the same for every column), staged once per workgroup.  Read from global memory stage by stage
     // instead, each twiddle load's s_waitcnt also waited for the previous prime's stores (one
     // counter for loads and stores), so compute and stores of consecutive primes never overlapped.
-    __shared__ Tw twc[MHE_MODUP_TWG > 0 ? MHE_MODUP_TWG * R : 1];
-    const int tid = threadIdx.x, sl = WV ? tid / TPS : tid % S, t = WV ? tid % TPS : tid / S;
+    __shared__ Tw twc[MHE_MODUP_TWG * R];
+    const int tid = threadIdx.x, sl = tid % S, t = tid / S;
     const int logC = log_n - LOGR;
     // 1-D grid of X column blocks x L digits x IG output-prime groups.  xcd: the IG groups of one
     // (column block, digit) get ids i, i + 8, ..., i + 8 (IG - 1) -- workgroups are dealt to the 8
@@ -1212,7 +1120,7 @@ __global__ __launch_bounds__(256, (FP && !MIX) ? MHE_MODUP_OCC : MHE_MODUP_OCC_I
     const u64 qJ = primes[J].q;
     // twiddles of the group's primes into LDS (16 B each: the FP table (w, w/q) or the integer one
     // (w, Shoup), whichever the prime's sweep uses); groups wider than MHE_MODUP_TWG read global
-    const bool twl_on = MHE_MODUP_TWG > 0 && i_hi - i_lo <= MHE_MODUP_TWG; // uniform per workgroup
+    const bool twl_on = i_hi - i_lo <= MHE_MODUP_TWG; // uniform per workgroup
     if (twl_on)
     {
         const int ng = i_hi - i_lo;
@@ -1272,7 +1180,7 @@ __global__ __launch_bounds__(256, (FP && !MIX) ? MHE_MODUP_OCC : MHE_MODUP_OCC_I
                     v[e] = red ? barrett64(xe, p) : xe;
                 }
             }
-            if constexpr (MHE_MODUP_STW && M != 0)
+            if constexpr (M != 0)
             {
                 // the first phase's twiddles as scalar loads (fwd_first_phase_s), issued with the prime's
                 // setup
@@ -1290,36 +1198,7 @@ __global__ __launch_bounds__(256, (FP && !MIX) ? MHE_MODUP_OCC : MHE_MODUP_OCC_I
                 for (int s = 0; s < LOGE; s++)
                     ar.template fwd<E>(v, 1 << (LOGE - 1 - s), [&](int e) { return (1 << s) + (e >> (LOGE - s)); });
             }
-            // MHE_MODUP_TPF: the twiddles of the first two stages after the transpose (1 and 2 per lane)
-            // read before it, so their LDS round trip overlaps the transpose's
-            [[maybe_unused]] TWA q4[1], q5[2];
-            if constexpr (MHE_MODUP_TPF && LOGE == 4 && LOGR == 8)
-            {
-                if (twl_on)
-                {
-                    q4[0] = tl[16 + t];
-                    if constexpr (MHE_MODUP_TPF > 1)
-                    {
-                        q5[0] = tl[32 + 2 * t];
-                        q5[1] = tl[32 + 2 * t + 1];
-                    }
-                }
-            }
-            if constexpr (WV)
-            {
-                // wslot is XOR-linear in e: row t + 16e sits at wslot(sl, t) ^ 17e, row 16t + e at
-                // wslot(sl, 16t) ^ e; the two bases go through an empty asm each output prime so the
-                // 32 slots are recomputed (one v_xor each) rather than hoisted into 32 VGPRs
-                u32 wb = (u32)wslot(sl, t), rb = (u32)wslot(sl, 16 * t);
-                asm volatile("" : "+v"(wb), "+v"(rb));
-                wave_lds_fence(); // the previous output prime's reads of this column come first
-#pragma unroll
-                for (int e = 0; e < E; e++) lds_v[wb ^ (17u * e)] = v[e];
-                wave_lds_fence();
-#pragma unroll
-                for (int e = 0; e < E; e++) v[e] = lds_v[rb ^ (u32)e];
-            }
-            else if constexpr (PG)
+            if constexpr (PG)
             {
                 // the asm markers keep the two read sequences apart: merged, they took their offsets
                 // from SGPRs, one v_add per read
@@ -1353,12 +1232,8 @@ __global__ __launch_bounds__(256, (FP && !MIX) ? MHE_MODUP_OCC : MHE_MODUP_OCC_I
             }
             if (twl_on)
             {
-                constexpr int S0 = (MHE_MODUP_TPF && LOGE == 4 && LOGR == 8) ? LOGE + (MHE_MODUP_TPF > 1 ? 2 : 1) : LOGE;
-                // stage 4: entry 16 + t; stage 5: 32 + 2t + (e >> 3)
-                if constexpr (S0 > LOGE) ar.template fwd_tab<E>(v, 1 << (LOGR - 1 - LOGE), q4, [&](int) { return 0; });
-                if constexpr (S0 > LOGE + 1) ar.template fwd_tab<E>(v, 1 << (LOGR - 2 - LOGE), q5, [&](int e) { return e >> 3; });
 #pragma unroll
-                for (int s = S0; s < LOGR; s++)
+                for (int s = LOGE; s < LOGR; s++)
                     ar.template fwd_tab<E>(v, 1 << (LOGR - 1 - s), tl,
                                            [&](int e) { return (1 << s) + ((E * t + e) >> (LOGR - s)); });
             }
@@ -1413,7 +1288,7 @@ __global__ __launch_bounds__(256, (FP && !MIX) ? MHE_MODUP_OCC : MHE_MODUP_OCC_I
 #pragma unroll
                 for (int e = 0; e < E; e++) st_nt<0>(d0 + (size_t)e * stride, ar.out(v[e]));
             }
-            if constexpr (!WV && (!PG || MHE_MODUP_PING_BAR)) lds_barrier(); // lds is rewritten by the next output prime (its stores need not land)
+            if constexpr (!PG) lds_barrier(); // lds is rewritten by the next output prime (its stores need not land)
         }
     };
     if constexpr (FP)
@@ -1430,10 +1305,7 @@ template <int LOGR, bool FP, bool MIX = false>
 static inline void modup_col_a(const KsPtrs &P, int B, const PrimeDev *primes, const Tw *tw, int L, int K,
                                int log_n, long long twd, int I0, int Icnt, int IG, int pack, hipStream_t st)
 {
-#ifndef MHE_MODUP_LOGT8
-#define MHE_MODUP_LOGT8 4
-#endif
-    constexpr int LOGT = LOGR <= 7 ? 3 : MHE_MODUP_LOGT8;
+    constexpr int LOGT = LOGR <= 7 ? 3 : 4;
     using SH = Shape<LOGR, LOGT>;
     const int subs = 1 << (log_n - LOGR);
     const int X = subs / SH::S;
@@ -1486,10 +1358,7 @@ enum PassKind
 // workgroups.
 // (r05t: with the grouped epilogue loads of the large launches applied everywhere instead, the
 // ResNet-20 batch ran at 1.398 instead of 1.450 images/s; the ops at 25-31 limbs measured equal)
-static inline long row_pre_max_wg()
-{
-    return 8192L;
-}
+constexpr long row_pre_max_wg = 8192L;
 
 template <int PASS, int LOGR, class Job, bool FP>
 static inline void launch_pass_a(const Job &job, int log_n, int jobs, long long twd, hipStream_t st)
@@ -1503,7 +1372,7 @@ static inline void launch_pass_a(const Job &job, int log_n, int jobs, long long 
     if constexpr (PASS == FWD_COL) hipLaunchKernelGGL((k_fwd_col<LOGR, LOGT, Job, FP>), grid, dim3(256), 0, st, job, log_n, twd);
     if constexpr (PASS == FWD_ROW)
     {
-        if constexpr (MHE_ROW3 && FP && LOGR == 8)
+        if constexpr (FP && LOGR == 8)
         {
             if (log_n == 16)
             {
@@ -1511,14 +1380,14 @@ static inline void launch_pass_a(const Job &job, int log_n, int jobs, long long 
                 return;
             }
         }
-        if ((long)grid.x * grid.y <= row_pre_max_wg())
+        if ((long)grid.x * grid.y <= row_pre_max_wg)
             hipLaunchKernelGGL((k_fwd_row<LOGR, LOGT, Job, FP, true>), grid, dim3(256), 0, st, job, log_n, twd);
         else
             hipLaunchKernelGGL((k_fwd_row<LOGR, LOGT, Job, FP, false>), grid, dim3(256), 0, st, job, log_n, twd);
     }
     if constexpr (PASS == INV_ROW)
     {
-        if constexpr (MHE_ROW3 && FP && LOGR == 8)
+        if constexpr (FP && LOGR == 8)
         {
             if (log_n == 16)
             {
@@ -1563,16 +1432,6 @@ static inline void launch_row(const Job &job, int log_n, int jobs, const NttMode
     }
 }
 
-// MHE_ICOL_PER=1..MHE_ICOL_G (A/B runs): output primes per lift workgroup, instead of the size rule
-static inline int icol_per_override()
-{
-    static const int v = [] {
-        const char *e = getenv("MHE_ICOL_PER");
-        const int x = e ? atoi(e) : 0;
-        return x >= 1 && x <= MHE_ICOL_G ? x : 0;
-    }();
-    return v;
-}
 // k_icol_lift over `polys` source polys (all batch entries: cs.per polys each) and `cnt` output
 // primes each (job index s * cnt + i), the column-pass shape of launch_col; IG groups of output
 // primes per (column block, poly)
@@ -1588,8 +1447,7 @@ static inline void icol_lift_a(const ColSrc &cs, const Job &job, int polys, int 
     // batched ones share the inverse stages over 2 to MHE_ICOL_G primes (ubench at 31 / 20 limbs, profiles/r03v:
     // 4 rescales 207 -> 185 us)
     const int jobs = polys * cnt;
-    int per = jobs >= 128 ? MHE_ICOL_G : jobs >= 56 ? 2 : 1;
-    if (const int po = icol_per_override()) per = po;
+    const int per = jobs >= 128 ? MHE_ICOL_G : jobs >= 56 ? 2 : 1;
     const int IG = (cnt + per - 1) / per;
     hipLaunchKernelGGL((k_icol_lift<LOGR, LOGT, Job, FP>), dim3(subs / SH::S, polys, IG), dim3(256), 0, st, cs, job,
                        cnt, log_n, dinv, dfwd);
@@ -1623,8 +1481,7 @@ static inline void col_lift2_a(const Job &job, int polys, int cnt, int log_n, lo
     using SH = Shape<LOGR, LOGT>;
     const int subs = 1 << (log_n - LOGR);
     const int jobs = polys * cnt;
-    int per = jobs >= 128 ? MHE_ICOL_G : jobs >= 56 ? 2 : 1; // as icol_lift_a
-    if (const int po = icol_per_override()) per = po;
+    const int per = jobs >= 128 ? MHE_ICOL_G : jobs >= 56 ? 2 : 1; // as icol_lift_a
     const int IG = (cnt + per - 1) / per;
     hipLaunchKernelGGL((k_col_lift2<LOGR, LOGT, Job>), dim3(subs / SH::S, polys, IG), dim3(256), 0, st, job, cnt, log_n,
                        dfwd);
@@ -1695,25 +1552,12 @@ __device__ __forceinline__ void row_stages(typename A::T (&v)[8], u32 t, int b_l
                                [&](int e) { return twz((1u << s) + (lay(t, e, b_lo) >> (LOGR - s))); });
 }
 
+// waves per SIMD the FP64 fused MAC at n = 2^16 is compiled for: 168 VGPRs, one LDS transpose buffer
+// (48 KB).  With the loads at the top of each digit (the sched_barrier in `step`) C2's k_ks_row_mac
+// 2743 -> 2698 us, ResNet-level ops equal (profiles/r06n); without them 3 waves were equal on C2 and 2 %
+// slower on single key switches (r06c)
+constexpr int MHE_KS_OCC = 3;
 template <int LOGR, bool FP, bool MIX = false>
-#ifndef MHE_KS_OCC
-#define MHE_KS_OCC 3 // waves per SIMD the FP64 fused MAC at n = 2^16 is compiled for: 168 VGPRs, one LDS
-                     // transpose buffer (48 KB).  With the loads at the top of each digit (MHE_KS_SB)
-                     // C2's k_ks_row_mac 2743 -> 2698 us, ResNet-level ops equal (profiles/r06n); without
-                     // them 3 waves were equal on C2 and 2 % slower on single key switches (r06c)
-#endif
-#ifndef MHE_KS_PP
-#define MHE_KS_PP 0 // digit loop unrolled twice, prefetched digit in alternating registers
-#endif
-#ifndef MHE_KS_KPF
-#define MHE_KS_KPF 0 // key limbs loaded one digit ahead too (32 VGPRs more)
-#endif
-#ifndef MHE_KS_SB
-#define MHE_KS_SB 1 // digit loop: key and next-digit loads issued at the top of the step (sched_barrier)
-#endif
-#ifndef MHE_KS_FL
-#define MHE_KS_FL 1 // keys and accumulators in the row transform's last layout (no transpose back per digit)
-#endif
 __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8) ? MHE_KS_OCC : 2) void k_ks_row_mac(KsPtrs P, const PrimeDev *__restrict__ primes,
                                                        const Tw *__restrict__ tw_all, int L, int K, int log_n,
                                                        long long twd, int I0, int pack, int kpack, int share,
@@ -1751,13 +1595,13 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8) ? MHE_KS_OCC : 2) vo
     constexpr int B_A = LOGR - 3, B_B = LOGR - 6;
     static_assert(LOGR >= 6, "the row transform ends in layout lay(t, e, 0)");
     // layout of the key limbs, the input limb and the accumulators: the row transform's last
-    // (lay(t, e, 0): 8 consecutive residues per lane) with MHE_KS_FL, so a digit needs no transpose
-    // back to the coalesced layout lay(t, e, B_A) -- the accumulators take it once, at the end
-    constexpr int BK = MHE_KS_FL ? 0 : B_A;
+    // (lay(t, e, 0): 8 consecutive residues per lane), so a digit needs no transpose back to the
+    // coalesced layout lay(t, e, B_A) -- the accumulators take it once, at the end
+    constexpr int BK = 0;
     // one transpose buffer is enough (every transpose stays inside one wave and a wave's LDS
     // operations complete in order; the fences only stop the compiler from reordering them):
     // 48 KB per workgroup fits 3 workgroups per CU, two buffers (64 KB) only 2
-    constexpr int XCH = (FP && !MIX && LOGR == 8 && MHE_KS_OCC >= 3) ? 1 : 2;
+    constexpr int XCH = (FP && !MIX && LOGR == 8) ? 1 : 2;
     __shared__ T xch[XCH][S * R];
     __shared__ TW twl[S * R];
     const int j0 = 0, j1 = L;
@@ -1817,7 +1661,6 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8) ? MHE_KS_OCC : 2) vo
         // so every iteration issues the same load instructions from the same per-lane offsets
         // (only the uniform base moves) -- with the input limb inside the loop, the compiler
         // selected between two offset sets and rebuilt 16 64-bit addresses per digit.  The loop is
-        // unrolled twice with the prefetched digit in alternating registers (no copies), and
         // instantiated per (packed intermediate, prepared key) pair, uniform per workgroup.  The
         // last digit's prefetch is repeated past the end: with a data-dependent load count the
         // compiler drained every load in flight (vmcnt(0)) at the top of each digit.
@@ -1961,8 +1804,6 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8) ? MHE_KS_OCC : 2) vo
 #pragma unroll
                 for (int e = 0; e < 8; e++) w[e] = x0[slot(sb, e, B_B)];
                 row_stages<LOGR>(w, t, B_B, 3, 6, mytw, ar);
-                T *xl = x1;
-                int bl = B_B;
                 if (LOGR > 6)
                 {
                     wave_lds_fence();
@@ -1972,37 +1813,17 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8) ? MHE_KS_OCC : 2) vo
 #pragma unroll
                     for (int e = 0; e < 8; e++) w[e] = x1[slot(s0, e, 0)];
                     row_stages<LOGR>(w, t, 0, 6, LOGR, mytw, ar);
-                    xl = x0;
-                    bl = 0;
                 }
-                if constexpr (MHE_KS_FL)
-                {
-                    // already the keys' layout (integer: canonical digits keep the 128-bit sums
-                    // exact for any digit count below 2^8)
-#pragma unroll
-                    for (int e = 0; e < 8; e++)
-                    {
-                        if constexpr (FPA)
-                            d[e] = w[e];
-                        else
-                            d[e] = ar.canon(w[e]);
-                    }
-                    return;
-                }
-                // back to the coalesced layout of the key stream (integer: canonical digits keep
-                // the 128-bit sums exact for any digit count below 2^8)
-                wave_lds_fence();
+                // already the keys' layout (integer: canonical digits keep the 128-bit sums
+                // exact for any digit count below 2^8)
 #pragma unroll
                 for (int e = 0; e < 8; e++)
                 {
                     if constexpr (FPA)
-                        xl[swz(lay(t, e, bl))] = w[e];
+                        d[e] = w[e];
                     else
-                        xl[swz(lay(t, e, bl))] = ar.canon(w[e]);
+                        d[e] = ar.canon(w[e]);
                 }
-                wave_lds_fence();
-#pragma unroll
-                for (int e = 0; e < 8; e++) d[e] = xl[swz(lay(t, e, B_A))];
             };
             u64 ka[8], kb[8], va[8], vb[8];
             if (nd > 0) load_inter(digit_of(0), va); // nd == 0: one data limb, output prime 0
@@ -2020,25 +1841,6 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8) ? MHE_KS_OCC : 2) vo
                 mac(d, ka, kb, false);
             }
             const int c0 = has_self ? 1 : 0; // digits taken before the loop
-#if MHE_KS_KPF
-            // keys one digit ahead as well: digit u's key limbs are in ka / kb when its step starts
-            if (nd > 0) load_key(digit_of(0), ka, kb);
-            auto step = [&](int u, const u64 (&cur)[8], u64 (&nxt)[8]) {
-                const int un = u + 1 < nd ? u + 1 : u;
-                u64 na[8], nb[8];
-                load_key(digit_of(un), na, nb);
-                load_inter(digit_of(un), nxt); // one digit ahead
-                T d[8];
-                ntt_digit(cur, d);
-                mac(d, ka, kb, ((u + c0) & 1) != 0);
-#pragma unroll
-                for (int e = 0; e < 8; e++)
-                {
-                    ka[e] = na[e];
-                    kb[e] = nb[e];
-                }
-            };
-#else
             auto step = [&](int u, const u64 (&cur)[8], u64 (&nxt)[8]) {
                 load_key(digit_of(u), ka, kb);
                 load_inter(digit_of(u + 1 < nd ? u + 1 : u), nxt); // one digit ahead
@@ -2046,28 +1848,17 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8) ? MHE_KS_OCC : 2) vo
                 // out a quarter into it and the copy of the prefetched digit at the end of the step
                 // waited for them (vmcnt(0)).  FP64 without MIX only: the integer and MIX variants
                 // spill already and spilled more
-                if constexpr (MHE_KS_SB && FP && !MIX) __builtin_amdgcn_sched_barrier(0);
+                if constexpr (FP && !MIX) __builtin_amdgcn_sched_barrier(0);
                 T d[8];
                 ntt_digit(cur, d);
                 mac(d, ka, kb, ((u + c0) & 1) != 0);
             };
-#endif
-#if MHE_KS_PP
-            int u = 0;
-            for (; u + 1 < nd; u += 2)
-            {
-                step(u, va, vb);
-                step(u + 1, vb, va);
-            }
-            if (u < nd) step(u, va, vb);
-#else
             for (int u = 0; u < nd; u++)
             {
                 step(u, va, vb);
 #pragma unroll
                 for (int e = 0; e < 8; e++) va[e] = vb[e];
             }
-#endif
         };
         using F0 = std::integral_constant<int, 0>;
         using F1 = std::integral_constant<int, 1>;
@@ -2111,7 +1902,6 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8) ? MHE_KS_OCC : 2) vo
                                        [&](int e) { return (rbi << s) + (lay(t, e, b_lo) >> (LOGR - s)); });
             };
             auto inv_rows = [&](T (&w)[8]) {
-                if constexpr (BK != 0) tr(w, BK, 0);
                 stages(w, 0, LOGR - 1, LOGR - 3);
                 tr(w, 0, 3);
                 stages(w, 3, LOGR - 4, LOGR > 6 ? LOGR - 6 : 0);
@@ -2162,21 +1952,18 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8) ? MHE_KS_OCC : 2) vo
                 c1v[e] = barrett128(a1[e].lo, a1[e].hi, p);
             }
         }
-        if constexpr (BK != B_A)
-        {
-            // one transpose per workgroup to the coalesced layout for the stores
-            u64 *xu = reinterpret_cast<u64 *>(x0);
-            auto back = [&](u64 (&v)[8]) {
-                wave_lds_fence();
+        // one transpose per workgroup to the coalesced layout for the stores
+        u64 *xu = reinterpret_cast<u64 *>(x0);
+        auto back = [&](u64 (&v)[8]) {
+            wave_lds_fence();
 #pragma unroll
-                for (int e = 0; e < 8; e++) xu[swz(lay(t, e, BK))] = v[e];
-                wave_lds_fence();
+            for (int e = 0; e < 8; e++) xu[swz(lay(t, e, BK))] = v[e];
+            wave_lds_fence();
 #pragma unroll
-                for (int e = 0; e < 8; e++) v[e] = xu[swz(lay(t, e, B_A))];
-            };
-            back(c0v);
-            back(c1v);
-        }
+            for (int e = 0; e < 8; e++) v[e] = xu[swz(lay(t, e, B_A))];
+        };
+        back(c0v);
+        back(c1v);
 #pragma unroll
         for (int e = 0; e < 8; e++)
         {

@@ -1,6 +1,6 @@
 #!/bin/bash
 # build/var/NAME/libmhe.so: an A/B variant of libmhe.so with extra compile flags, e.g.
-#   bash scripts/build_var.sh base -DMHE_ROW_PRE=0
+#   bash scripts/build_var.sh nt0 -DMHE_NT=0
 # Loaded by the Python binding with MHE_LIB_PATH=build/var/NAME/libmhe.so.
 set -eu
 NAME=$1; shift
