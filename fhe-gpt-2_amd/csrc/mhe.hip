@@ -191,12 +191,16 @@ struct Workspace
     u64 *hoist[MHE_MAXB] = {};
     u64 *hacc[MHE_MAXB * MHE_HOIST_R] = {}; // [2][K][n] key products of each hoisted rotation
     int *flags = nullptr;
+    // mhe_rotate_sum: per group in flight (MHE_MAXB) the sum of the key products A [2][L+1][n] and the
+    // sum of the lifted special limbs T [2][L][n], L = rs_limbs; allocated by the first call
+    u64 *rs_base = nullptr;
+    int rs_limbs = 0;
     // kernel timing (mhe_ctx_set_timing): event pairs recorded around the two dominant
     // key-switch kernels on this stream, read back by mhe_kernel_time
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[2];
     size_t ev_used[2] = { 0, 0 };
-    // device bytes of base / hoist_base: written under mu, read by mhe_scratch_bytes without it
-    std::atomic<size_t> bytes{ 0 }, hoist_bytes{ 0 };
+    // device bytes of base / hoist_base / rs_base: written under mu, read by mhe_scratch_bytes without it
+    std::atomic<size_t> bytes{ 0 }, hoist_bytes{ 0 }, rs_bytes{ 0 };
     int hoist_limbs = 0;                // the hoisting buffers' level (per-input ModUp of up to this many limbs)
     std::mutex mu;                      // growth of this stream's buffers
 };
@@ -245,6 +249,7 @@ struct mhe_ctx
     std::atomic<int> hoist_check{ 0 }; // recompute every hoisted rotation by the classic path and compare (mhe_ctx_set_hoist)
     std::atomic<int> fail_switch{ 0 }; // mhe_debug_fail_switch: the n-th next batched key switch fails (0: off)
     std::atomic<unsigned long long> hoist_rot{ 0 }, hoist_mac{ 0 }, hoist_bad{ 0 }; // mhe_hoist_stats
+    std::atomic<unsigned long long> rotsum_sums{ 0 }, rotsum_terms{ 0 };             // mhe_rotsum_stats
     std::atomic<int> fail_alloc{ 0 }; // mhe_debug_fail_alloc: the n-th next allocation fails (0: off)
     TwF *cmodf = nullptr; // [K][K]: (q_j mod q_i, (q_j mod q_i) / q_i) as doubles, j major (hoist.h)
     std::mutex mask_mu;
@@ -1369,6 +1374,69 @@ __global__ void k_galois_b(GalPtrs P, int log_n, size_t total)
     out[g] = in[base + src];
 }
 
+// mhe_rotate_sum: the key products of a chunk's entries folded into their groups' accumulators,
+// before the one ModDown forward NTT per limb of each group.  A chunk's entries come sorted by key
+// (they share the key stream of the MAC), so a group's entries are anywhere in it: zof[e] is the
+// chunk's group of entry e.  Every special limb has been through its own inverse NTT ([0, 2P)), so
+// each lift is SEAL's integer (evaluator.cpp:2466-2524) and the sums that follow are sums of
+// canonical residues mod q_i: the special limbs are never added mod P.
+struct RotSumPtrs
+{
+    const u64 *acc[MHE_MAXB];  // entry: key products [2][L+1][n], special limbs in coefficient form
+    const u64 *perm[MHE_MAXB]; // entry: permuted c0 [L][n]
+    u64 *A[MHE_MAXB];          // group: sum of the key products [2][L+1][n] (limbs 0 .. L-1 used)
+    u64 *T[MHE_MAXB];          // group: sum of the lifted special limbs [2][L][n], coefficient form
+    u64 *out[MHE_MAXB];        // group: out[0] += (or =) the permuted c0s
+    int zof[MHE_MAXB];         // entry: its group among the chunk's
+    int B;                     // entries in the chunk
+    int first[MHE_MAXB];       // group: its first chunk (A and T written, not added to)
+    int write0[MHE_MAXB];      // group: out[0] written, not added to (first chunk without accumulate)
+};
+
+// grid (n / 512, 2 * L, groups in the chunk); one lane owns two adjacent words of (group, k, i)
+__global__ __launch_bounds__(256) void k_rotsum_acc(RotSumPtrs P, const PrimeDev *__restrict__ primes, int L, int K,
+                                                    int log_n)
+{
+    const int z = blockIdx.z, k = blockIdx.y / L, i = blockIdx.y - k * L;
+    const size_t x = ((size_t)blockIdx.x * 256 + threadIdx.x) * 2;
+    const size_t n = (size_t)1 << log_n;
+    JobModDownCol::View v; // the ModDown column pass's lift, with its constants
+    v.p = prime_at(primes, i);
+    v.P = prime_at(primes, K - 1);
+    v.half = v.P.q >> 1;
+    v.fix = v.p.q - barrett64(v.half, v.p);
+    v.reduce = v.P.q > v.p.q;
+    const u64 q = v.p.q;
+    const size_t oa = (size_t)(k * (L + 1) + i) * n + x, os = (size_t)(k * (L + 1) + L) * n + x;
+    const size_t ot = (size_t)(k * L + i) * n + x, oc = (size_t)i * n + x;
+    ulonglong2 a{ 0, 0 }, t{ 0, 0 }, c0{ 0, 0 };
+    if (!P.first[z])
+    {
+        a = *(const ulonglong2 *)(P.A[z] + oa);
+        t = *(const ulonglong2 *)(P.T[z] + ot);
+    }
+    if (k == 0 && !P.write0[z]) c0 = *(const ulonglong2 *)(P.out[z] + oc);
+    for (int e = 0; e < P.B; e++)
+    {
+        if (P.zof[e] != z) continue; // uniform over the workgroup
+        const ulonglong2 ae = *(const ulonglong2 *)(P.acc[e] + oa);
+        const ulonglong2 se = *(const ulonglong2 *)(P.acc[e] + os);
+        a.x = addmod(a.x, ae.x, q);
+        a.y = addmod(a.y, ae.y, q);
+        t.x = addmod(t.x, csub(v.lift(se.x), q), q); // lift() is in [0, 2q)
+        t.y = addmod(t.y, csub(v.lift(se.y), q), q);
+        if (k == 0)
+        {
+            const ulonglong2 ce = *(const ulonglong2 *)(P.perm[e] + oc);
+            c0.x = addmod(c0.x, ce.x, q);
+            c0.y = addmod(c0.y, ce.y, q);
+        }
+    }
+    *(ulonglong2 *)(P.A[z] + oa) = a;
+    *(ulonglong2 *)(P.T[z] + ot) = t;
+    if (k == 0) *(ulonglong2 *)(P.out[z] + oc) = c0;
+}
+
 // Bootstrapper::modraise_inplace (ckks_bootstrapping/Bootstrapper.cpp:2894-2948): the single-limb
 // coefficient-form polynomial x (mod q_0, canonical) is lifted centered, v = x - q_0 if
 // x > q_0/2, and reduced mod every prime of the target level.
@@ -1793,7 +1861,11 @@ static void run_moddown(mhe_ctx *c, const KsJob *jobs, int B, int L, Workspace *
 // rescale_out [2][L-1][n] (JobMDRCol / JobMDRRow); ct limb L-1 is overwritten on the way.
 // c1_write: ct[1] is taken as zero and written, not read (target may then alias ct[1]: it is last
 // read by the key MAC, before the ModDown writes ct).
-static int run_switch_key_batch(mhe_ctx *c, const KsJob *jobs, int B, int L, hipStream_t st, int c1_write = 0)
+// front != nullptr (mhe_rotate_sum; fused key MAC only): stop before the ModDown, the key products
+// left in the entries' scratch (w->e[e].acc), ct untouched; *front = the key MAC already ran the
+// special limbs' inverse row pass.
+static int run_switch_key_batch(mhe_ctx *c, const KsJob *jobs, int B, int L, hipStream_t st, int c1_write = 0,
+                                int *front = nullptr)
 {
     if (B < 1 || B > MHE_MAXB) return fail(MHE_ERR_ARG, "key switch: batch size out of range");
     // mhe_debug_fail_switch's countdown (tests): this launch sequence fails before its first launch
@@ -1909,7 +1981,10 @@ static int run_switch_key_batch(mhe_ctx *c, const KsJob *jobs, int B, int L, hip
                                c->K, jobs[0].key_limbs, log_n, I0);
         }
     }
-    run_moddown(c, jobs, B, L, w, special_inv_done, c1_write, st);
+    if (front)
+        *front = special_inv_done;
+    else
+        run_moddown(c, jobs, B, L, w, special_inv_done, c1_write, st);
     HIP_LAUNCH_CHECK();
     return MHE_OK;
 }
@@ -2218,6 +2293,7 @@ MHE_EXPORT int mhe_ctx_destroy(mhe_ctx *c)
     {
         if (kv.second.base) (void)hipFree(kv.second.base);
         if (kv.second.hoist_base) (void)hipFree(kv.second.hoist_base);
+        if (kv.second.rs_base) (void)hipFree(kv.second.rs_base);
         if (kv.second.flags) (void)hipFree(kv.second.flags);
         for (auto &v : kv.second.ev)
             for (auto &e : v)
@@ -2610,7 +2686,7 @@ MHE_EXPORT int mhe_scratch_bytes(mhe_ctx *c, uint64_t *workspace, uint64_t *hois
         *workspace = *hoisting = 0;
         for (auto &kv : c->ws)
         {
-            *workspace += kv.second.bytes;
+            *workspace += kv.second.bytes + kv.second.rs_bytes;
             *hoisting += kv.second.hoist_bytes;
         }
         *streams = (int)c->ws.size();
@@ -2665,6 +2741,7 @@ MHE_EXPORT int mhe_stream_destroy(mhe_ctx *c, void *stream)
             (void)hipStreamSynchronize(S(stream));
             if (it->second.base) (void)hipFree(it->second.base);
             if (it->second.hoist_base) (void)hipFree(it->second.hoist_base);
+            if (it->second.rs_base) (void)hipFree(it->second.rs_base);
             if (it->second.flags) (void)hipFree(it->second.flags);
             for (auto &v : it->second.ev)
                 for (auto &e : v)
@@ -3767,6 +3844,213 @@ MHE_EXPORT int mhe_apply_galois_batch(mhe_ctx *c, int count, const uint64_t *con
         HIP_LAUNCH_CHECK();
         if ((r = run_switch_key_batch(c, jobs, B, limbs, st, 1))) return r;
     }
+    return MHE_OK;
+}
+
+// ------------------------------------------------------------------------------ rotate and sum
+// The scratch of mhe_rotate_sum on stream st: the workspace for `entries` batch entries and the
+// accumulators of MHE_MAXB groups at L limbs (grown, after draining the stream, when a call needs a
+// higher level).
+static int get_rotsum(mhe_ctx *c, hipStream_t st, int entries, int L, Workspace **out)
+{
+    Workspace *w;
+    int r = get_ws(c, st, c->K - 1, &w, entries);
+    if (r) return r;
+    std::lock_guard<std::mutex> g(w->mu);
+    if (w->rs_limbs < L)
+    {
+        HIP_TRY(hipSetDevice(c->device));
+        if (w->rs_base)
+        {
+            HIP_TRY(hipStreamSynchronize(st));
+            HIP_TRY(hipFree(w->rs_base));
+        }
+        w->rs_base = nullptr;
+        w->rs_limbs = 0;
+        w->rs_bytes = 0;
+        const size_t bytes = (size_t)MHE_MAXB * (4 * (size_t)L + 2) * c->n * sizeof(u64);
+        if (injected_alloc_failure(c) || scratch_alloc((void **)&w->rs_base, bytes) != hipSuccess)
+        {
+            w->rs_base = nullptr;
+            return fail(MHE_ERR_MEMORY, "workspace allocation failed");
+        }
+        w->rs_limbs = L;
+        w->rs_bytes = bytes;
+    }
+    *out = w;
+    return MHE_OK;
+}
+
+MHE_EXPORT int mhe_rotsum_stats(mhe_ctx *c, uint64_t *sums, uint64_t *terms, int reset)
+{
+    if (!valid_ctx(c) || !sums || !terms) return fail(MHE_ERR_ARG, "invalid argument");
+    *sums = reset ? c->rotsum_sums.exchange(0) : c->rotsum_sums.load();
+    *terms = reset ? c->rotsum_terms.exchange(0) : c->rotsum_terms.load();
+    return MHE_OK;
+}
+
+MHE_EXPORT int mhe_rotate_sum(mhe_ctx *c, int count, const uint64_t *const *in, const uint32_t *elts,
+                              const uint64_t *const *keys, const int *key_limbs, const int *group, int groups,
+                              uint64_t *const *out, int accumulate, int limbs, void *s)
+{
+    int r = check_limbs(c, limbs, 1);
+    if (r) return r;
+    if (count < 0 || groups < 0 || (count && (!in || !elts || !keys || !key_limbs || !group)) || (groups && !out))
+        return fail(MHE_ERR_ARG, "invalid argument");
+    hipStream_t st = S(s);
+    const int L = limbs;
+    const size_t n = c->n, ps = (size_t)L << c->log_n;
+    // group[] non-decreasing from 0 to groups - 1 without a gap: no group is empty
+    for (int i = 0, prev = 0; i < count; prev = group[i++])
+        if (group[i] != prev && !(i > 0 && group[i] == prev + 1)) return fail(MHE_ERR_ARG, "invalid argument");
+    if ((count ? group[count - 1] + 1 : 0) != groups) return fail(MHE_ERR_ARG, "invalid argument");
+    for (int g = 0; g < groups; g++)
+        if (!out[g]) return fail(MHE_ERR_ARG, "Galois key not present");
+    for (int i = 0; i < count; i++)
+    {
+        if (!in[i] || !keys[i]) return fail(MHE_ERR_ARG, "Galois key not present");
+        if (!(elts[i] & 1) || elts[i] >= 2 * c->n) return fail(MHE_ERR_ARG, "Galois element is not valid");
+        // every key is checked before the first launch, so a bad key leaves no output half-written
+        if (key_limbs[i] < limbs + 1 || key_limbs[i] > c->K)
+            return fail(MHE_ERR_ARG, "kswitch_keys is not valid for encryption parameters");
+    }
+    // outputs must be disjoint from every input and from each other (a group's output is written
+    // while later chunks still read their inputs)
+    for (int g = 0; g < groups; g++)
+    {
+        for (int i = 0; i < count; i++)
+            if (ranges_overlap(out[g], 2 * ps, in[i], 2 * ps))
+                return fail(MHE_ERR_ARG, "result cannot point to the same value as operand");
+        for (int h = 0; h < g; h++)
+            if (ranges_overlap(out[g], 2 * ps, out[h], 2 * ps))
+                return fail(MHE_ERR_ARG, "result cannot point to the same value as operand");
+    }
+    if (!count) return MHE_OK;
+    if (!c->galois_fused || !c->ks_fused)
+    {
+        // the debugging paths: rotate one by one and add
+        u64 *tmp = nullptr;
+        if (injected_alloc_failure(c) || mhe_internal_alloc((void **)&tmp, 2 * ps * sizeof(u64), st) != hipSuccess)
+            return fail(MHE_ERR_MEMORY, "device allocation failed");
+        for (int i = 0; i < count && !r; i++)
+        {
+            const bool first = (i == 0 || group[i] != group[i - 1]) && !accumulate;
+            u64 *o = out[group[i]];
+            r = mhe_apply_galois_to(c, in[i], first ? o : tmp, elts[i], keys[i], key_limbs[i], limbs, s);
+            if (!r && !first) r = launch_addsub(c, o, tmp, o, 2, limbs, 0, s);
+        }
+        (void)mhe_internal_free(tmp, st);
+        if (r) return r;
+        c->rotsum_sums += (unsigned long long)groups;
+        c->rotsum_terms += (unsigned long long)count;
+        return MHE_OK;
+    }
+    // all scratch before the first launch: a failed growth leaves every output as it was
+    Workspace *w;
+    if ((r = get_rotsum(c, st, std::min(count, MHE_MAXB), L, &w))) return r;
+    const size_t rs_per = (4 * (size_t)w->rs_limbs + 2) * n;
+    auto A_of = [&](int slot) { return w->rs_base + (size_t)slot * rs_per; };
+    auto T_of = [&](int slot) { return A_of(slot) + 2 * (size_t)(L + 1) * n; };
+    // rounds of at most MHE_MAXB groups: their entries, those of one key side by side (a launch of
+    // them shares the key stream, k_ks_row_mac share), in chunks of at most MHE_MAXB that cut across
+    // groups, then one ModDown forward NTT per limb for all of the round's groups
+    std::vector<int> order(count);
+    for (int i = 0; i < count; i++) order[i] = i;
+    int i0 = 0;
+    for (int g0 = 0; g0 < groups; g0 += MHE_MAXB)
+    {
+        const int G = std::min(MHE_MAXB, groups - g0);
+        int i1 = i0;
+        while (i1 < count && group[i1] < g0 + G) i1++;
+        std::stable_sort(order.begin() + i0, order.begin() + i1, [&](int a, int b) { return keys[a] < keys[b]; });
+        bool started[MHE_MAXB] = {}; // the round's groups that a chunk has written
+        for (int b0 = i0; b0 < i1; b0 += MHE_MAXB)
+        {
+            const int B = std::min(MHE_MAXB, i1 - b0);
+            // permuted (c0, c1) of every entry into its scratch, then the key switch of the permuted c1
+            // up to the key products (evaluator.cpp:2193-2214, 2281-2463)
+            GalPtrs gp{};
+            KsJob jobs[MHE_MAXB];
+            RotSumPtrs rp{};
+            int Z = 0, zslot[MHE_MAXB];
+            rp.B = B;
+            for (int e = 0; e < B; e++)
+            {
+                const int i = order[b0 + e];
+                gp.in[e] = in[i];
+                gp.out[e] = w->e[e].ct3;
+                gp.elt[e] = elts[i];
+                jobs[e] = KsJob{ nullptr, w->e[e].ct3 + ps, keys[i], key_limbs[i], nullptr };
+                rp.acc[e] = w->e[e].acc;
+                rp.perm[e] = w->e[e].ct3;
+                const int slot = group[i] - g0;
+                int z = 0;
+                while (z < Z && zslot[z] != slot) z++;
+                if (z == Z)
+                {
+                    zslot[Z++] = slot;
+                    rp.A[z] = A_of(slot);
+                    rp.T[z] = T_of(slot);
+                    rp.out[z] = out[group[i]];
+                    rp.first[z] = started[slot] ? 0 : 1; // the group's first chunk
+                    rp.write0[z] = (!started[slot] && !accumulate) ? 1 : 0;
+                    started[slot] = true;
+                }
+                rp.zof[e] = z;
+            }
+            const size_t total = 2 * ps;
+            count_op(c, MHE_OPK_GALOIS, L, 2ull * B);
+            hipLaunchKernelGGL(k_galois_b, dim3((unsigned)((total + 255) / 256), (unsigned)B), dim3(256), 0, st, gp,
+                               c->log_n, total);
+            HIP_LAUNCH_CHECK();
+            int special_inv_done = 0;
+            if ((r = run_switch_key_batch(c, jobs, B, L, st, 0, &special_inv_done))) return r;
+            // each entry's special limbs through their own inverse NTT, [0, 2P)
+            JobB<JobStrided> sj;
+            sj.per = 2;
+            for (int e = 0; e < B; e++)
+                sj.j[e] = JobStrided{ w->e[e].acc + (size_t)L * n, w->e[e].acc + (size_t)L * n, (size_t)(L + 1) * n,
+                                      (size_t)(L + 1) * n, c->K - 1, 0, c->primes, c->itw, c->log_n, 0 };
+            if (!special_inv_done) inv_row(sj, c->log_n, 2 * B, c->nm, st);
+            inv_col(sj, c->log_n, 2 * B, c->nm, st);
+            hipLaunchKernelGGL(k_rotsum_acc, dim3((unsigned)(n / 512), (unsigned)(2 * L), (unsigned)Z), dim3(256), 0, st,
+                               rp, c->primes, L, c->K, c->log_n);
+            HIP_LAUNCH_CHECK();
+        }
+        // the round's groups: T -> NTT(T) in place, then out += (A - NTT(T)) P^-1 (out[1] written
+        // when not accumulating)
+        JobB<JobFwdPlain> fc;
+        fc.per = 2 * L;
+        JobB<JobModDownRow> dr;
+        dr.per = 2 * L;
+        for (int z = 0; z < G; z++)
+        {
+            JobFwdPlain f;
+            f.src = T_of(z);
+            f.dst = T_of(z);
+            f.primes = c->primes;
+            f.tw = c->tw;
+            f.limbs = L;
+            f.log_n = c->log_n;
+            f.mode = 0;
+            fc.j[z] = f;
+            dr.j[z] = JobModDownRow{ T_of(z), A_of(z), out[g0 + z], c->primes, c->tw, c->invq, L, c->K, c->log_n };
+            dr.j[z].fp = c->nm.fp ? 1 : 0;
+            dr.j[z].c1_write = accumulate ? 0 : 1;
+        }
+        fwd_col(fc, c->log_n, 2 * L * G, c->nm, st);
+        fwd_row(dr, c->log_n, 2 * L * G, c->nm, st);
+        HIP_LAUNCH_CHECK();
+        for (int z = 0; z < G; z++)
+        {
+            int terms = 0;
+            for (int i = i0; i < i1; i++) terms += group[i] == g0 + z;
+            count_op(c, MHE_OPK_ADDSUB, L, 2ull * (unsigned long long)(terms - 1 + (accumulate ? 1 : 0)));
+        }
+        i0 = i1;
+    }
+    c->rotsum_sums += (unsigned long long)groups;
+    c->rotsum_terms += (unsigned long long)count;
     return MHE_OK;
 }
 

@@ -227,6 +227,12 @@ public:
     std::size_t cached_plaintexts() const { return pt_cache_.size(); }
     std::size_t verify_cache(); // debugging aid: re-encode and compare every cached plaintext
 
+    // the giant-step sums of the BSGS transforms through Evaluator::rotate_sum (the same words and
+    // scale, one ModDown forward NTT per limb per sum).  Off by default; MHE_BOOT_ROTSUM=1 in the
+    // environment, read once at construction, starts it on.
+    void set_merged_giant_sums(bool on) { merged_giant_sums_ = on; }
+    bool merged_giant_sums() const { return merged_giant_sums_; }
+
 private:
     // the giant-step rotations of a BSGS transform in batched launches, then the outer sum
     void giant_rotate_sum(std::vector<seal::Ciphertext> &giantct, std::vector<seal::Ciphertext> &rotct, int first,
@@ -249,4 +255,5 @@ private:
         bool operator<(const PtKey &o) const;
     };
     std::map<PtKey, seal::Plaintext> pt_cache_;
+    bool merged_giant_sums_ = false;
 };

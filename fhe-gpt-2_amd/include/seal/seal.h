@@ -880,6 +880,17 @@ public:
     // must be distinct objects, none of them an input.
     void rotate_vectors(const std::vector<const Ciphertext *> &encrypted, const std::vector<int> &steps,
                         const GaloisKeys &galois_keys, const std::vector<Ciphertext *> &destinations) const;
+    // (not SEAL API) destination = sum_i rotate_vector(*encrypted[i], steps[i]), the words and scale of
+    // rotating one by one and folding with add_inplace_reduced_error in order
+    // (Bootstrapper.cpp:1990-2015: the giant-step sum of a BSGS transform).  Terms of one level with
+    // their keys present run as one mhe_rotate_sum: every rotation keeps its own key switch up to the
+    // lift of its special limb, and one ModDown forward NTT per limb serves the whole sum; a term
+    // with step 0 is a plain addend.  Unequal levels, a missing key (NAF decomposition), a size-3
+    // or non-NTT input, batched launches off or an enabled trace run rotate_vectors and
+    // add_inplace_reduced_error instead (a traced run records the same rotate / add_re records).
+    // destination may be one of the inputs; when the call throws it keeps its contents.
+    void rotate_sum(const std::vector<const Ciphertext *> &encrypted, const std::vector<int> &steps,
+                    const GaloisKeys &galois_keys, Ciphertext &destination) const;
     // (not SEAL API) rescale_to_next_inplace of independent ciphertexts in batched launches
     void rescale_to_next_inplace_many(const std::vector<Ciphertext *> &encrypted) const;
     // (not SEAL API) relinearize_inplace of independent size-3 ciphertexts: entries of one level run
@@ -996,6 +1007,9 @@ private:
     friend struct Lockstep::Impl;
     friend class FiberBatch;
     void lockstep_execute(std::vector<LsOp *> &ops) const;
+    // rotate_sum of every op (one mhe_rotate_sum, one group per op); false, with nothing written,
+    // when an op has to take the one-by-one path
+    bool rotate_sum_merged(const std::vector<LsOp *> &ops) const;
     std::size_t limbs_of(const parms_id_type &id) const;
     SEALContext context_;
     CKKSEncoder &encoder_;

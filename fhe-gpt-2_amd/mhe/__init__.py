@@ -85,6 +85,11 @@ SIGNATURES = {
     "mhe_apply_galois_batch": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, ctypes.POINTER(ctypes.c_uint32), vp,
                                               ctypes.POINTER(ctypes.c_int), ctypes.c_int, vp]),
     "mhe_rescale_batch": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, vp]),
+    "mhe_rotate_sum": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.POINTER(ctypes.c_uint32), vp,
+                                      ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.c_int, vp,
+                                      ctypes.c_int, ctypes.c_int, vp]),
+    "mhe_rotsum_stats": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                        ctypes.c_int]),
     "mhe_switch_key_batch": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
                                             vp]),
     "mhe_mod_switch_drop": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.c_int, vp]),
@@ -417,6 +422,28 @@ class Engine:
         _check(lib().mhe_apply_galois_batch(self._h, cnt, self._ptrs(cts), self._ptrs(outs), e, self._ptrs(keys), kl,
                                             cts[0].shape[1], self.stream()))
         return outs
+
+    def rotate_sum(self, cts, elts, keys, groups=None, outs=None, accumulate=False):
+        """mhe_rotate_sum: outs[g] (+)= the sum of the rotations of group g's entries (groups[i]: the
+        group of entry i, non-decreasing from 0; None: one group), one ModDown forward NTT per limb
+        per group."""
+        cnt = len(cts)
+        groups = [0] * cnt if groups is None else [int(g) for g in groups]
+        ng = (max(groups) + 1) if groups else 0
+        outs = [self.empty(*cts[0].shape) for _ in range(ng)] if outs is None else outs
+        e = (ctypes.c_uint32 * cnt)(*[int(x) for x in elts])
+        kl = (ctypes.c_int * cnt)(*[self._key_limbs(k) for k in keys])
+        gr = (ctypes.c_int * cnt)(*groups)
+        L = (cts[0] if cts else outs[0]).shape[1] if (cts or outs) else 1
+        _check(lib().mhe_rotate_sum(self._h, cnt, self._ptrs(cts), e, self._ptrs(keys), kl, gr, len(outs),
+                                    self._ptrs(outs), 1 if accumulate else 0, L, self.stream()))
+        return outs
+
+    def rotsum_stats(self, reset=False):
+        """mhe_rotsum_stats: (groups summed, entries rotated) by rotate_sum."""
+        s, t = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().mhe_rotsum_stats(self._h, ctypes.byref(s), ctypes.byref(t), 1 if reset else 0))
+        return s.value, t.value
 
     def rescale_batch(self, cts, outs=None):
         size, L = cts[0].shape[0], cts[0].shape[1]

@@ -1164,6 +1164,8 @@ Bootstrapper::Bootstrapper(long _loge, long _logn, long _logNh, long _L, double 
       evaluator(_evaluator), relin_keys(_relin_keys), gal_keys(_gal_keys)
 {
     // Bootstrapper.cpp:3-17
+    const char *rs = std::getenv("MHE_BOOT_ROTSUM");
+    merged_giant_sums_ = rs && rs[0] == '1';
     mod_reducer = std::make_unique<ModularReducer>(boundary_K, (double)loge, sin_cos_deg, scale_factor, inverse_deg,
                                                    context, encoder, encryptor, evaluator, relin_keys, decryptor);
 }
@@ -1802,6 +1804,20 @@ void Bootstrapper::giant_rotate_sum(std::vector<Ciphertext> &giantct, std::vecto
     // giant step i = first + k: rotate its inner sum by i * gs * basicstep (i != 0), then
     // tmpct = sum over k in order (Bootstrapper.cpp:1990-2015 / 2059-2084)
     const int nh = (int)Nh;
+    if (merged_giant_sums_)
+    {
+        // the same sum as one Evaluator::rotate_sum: one ModDown forward NTT per limb for the whole sum
+        std::vector<const Ciphertext *> terms;
+        std::vector<int> steps;
+        for (std::size_t k = 0; k < giantct.size(); k++)
+        {
+            const int i = first + (int)k;
+            terms.push_back(&giantct[k]);
+            steps.push_back(i == 0 ? 0 : (nh + i * gs * basicstep) % nh);
+        }
+        evaluator.rotate_sum(terms, steps, gal_keys, rtncipher);
+        return;
+    }
     std::vector<const Ciphertext *> in;
     std::vector<int> st;
     std::vector<Ciphertext *> out;

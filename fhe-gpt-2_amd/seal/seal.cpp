@@ -82,7 +82,8 @@ struct LsOp
         ROT,
         RESC,
         RELIN,
-        MULRE
+        MULRE,
+        ROTSUM // in / steps: the terms, out[0]: the sum
     } kind = ROT;
     std::vector<const Ciphertext *> in, in2;
     std::vector<int> steps;
@@ -2628,6 +2629,7 @@ void Evaluator::lockstep_execute(std::vector<LsOp *> &ops) const
                 else
                     multiply_reduced_error(*o.in[0], *o.in2[0], *o.rk, *o.out[0]);
                 break;
+            case LsOp::ROTSUM: rotate_sum(o.in, o.steps, *o.gk, *o.out[0]); break;
             }
         }
         catch (...)
@@ -2644,6 +2646,14 @@ void Evaluator::lockstep_execute(std::vector<LsOp *> &ops) const
     }
     try
     {
+        if (ops[0]->kind == LsOp::ROTSUM)
+        {
+            // one group per member, every sum through a temporary; members that cannot share the
+            // call (levels, missing keys) run alone
+            if (!rotate_sum_merged(ops))
+                for (LsOp *o : ops) run_one(*o);
+            return;
+        }
         // the members' entries as one batch; an output that is also an input (in place) or repeated
         // goes through a temporary
         std::vector<const Ciphertext *> in, in2;
@@ -2686,7 +2696,7 @@ void Evaluator::lockstep_execute(std::vector<LsOp *> &ops) const
     catch (...)
     {
         // The merged call validates every entry before its first launch (rescale / relinearize), or
-        // wrote only outputs that are not inputs (rotations, products through temporaries), so the
+        // wrote only outputs that are not inputs (rotations, products and sums through temporaries), so the
         // members' operands are unchanged here: each member's call runs again on its own and gets
         // its own result or its own error, as without the group.  Counted (merged_call_fallbacks):
         // a fallback means a merged launch failed, which a healthy run never sees.
@@ -2786,6 +2796,132 @@ void Evaluator::rotate_vectors(const std::vector<const Ciphertext *> &encrypted,
     if (tsc.top())
         for (std::size_t i = 0; i < encrypted.size(); i++)
             trace::record("rotate", { tin[i] }, trace::ct(*destinations[i]), "\"step\": " + std::to_string(steps[i]));
+}
+
+bool Evaluator::rotate_sum_merged(const std::vector<LsOp *> &ops) const
+{
+    if (!batched_launches() || trace::enabled() || ops.empty()) return false;
+    if (ops[0]->gk->parms_id() != context_.key_parms_id()) return false;
+    const parms_id_type &pid = ops[0]->in.empty() || !ops[0]->in[0] ? parms_id_zero : ops[0]->in[0]->parms_id();
+    std::size_t total = 0;
+    for (const LsOp *o : ops)
+    {
+        if (o->in.empty() || o->in.size() != o->steps.size() || o->gk != ops[0]->gk) return false;
+        std::size_t rotated = 0;
+        for (std::size_t i = 0; i < o->in.size(); i++)
+        {
+            const Ciphertext *c = o->in[i];
+            if (!c || c->size() != 2 || !c->is_ntt_form() || c->parms_id() != pid) return false;
+            if (o->steps[i] == 0) continue;
+            const std::uint32_t e = mhe_galois_elt_from_step(__builtin_ctzll(c->poly_modulus_degree()), o->steps[i]);
+            if (!e || !o->gk->has_key(e)) return false;
+            rotated++;
+        }
+        if (!rotated) return false; // plain adds only
+        total += rotated;
+    }
+    const Level lv = check_ct(context_, *ops[0]->in[0], "encrypted");
+    void *s = context_.stream();
+    // every sum into a temporary: a destination may be an input, and keeps its contents when the
+    // call throws.  A sum starts from its step-0 terms, if any, and the rotations accumulate.
+    std::vector<Ciphertext> res(ops.size());
+    auto has_addend = [](const LsOp *o) { return std::find(o->steps.begin(), o->steps.end(), 0) != o->steps.end(); };
+    const bool accumulate = has_addend(ops[0]);
+    for (const LsOp *o : ops)
+        if (has_addend(o) != accumulate) return false; // (members of a group run the same code)
+    for (std::size_t g = 0; g < ops.size(); g++)
+    {
+        const LsOp &o = *ops[g];
+        bool started = false;
+        for (std::size_t i = 0; i < o.in.size(); i++)
+        {
+            if (o.steps[i] != 0) continue;
+            check_ct(context_, *o.in[i], "encrypted");
+            if (!started)
+                res[g] = *o.in[i];
+            else
+            {
+                res[g].scale() = o.in[i]->scale(); // add_inplace_reduced_error at equal levels
+                add_inplace(res[g], *o.in[i]);
+            }
+            started = true;
+        }
+        if (!started) fresh_dest(context_, *o.in[0], res[g], 2);
+    }
+    std::vector<const std::uint64_t *> in, keys;
+    std::vector<std::uint32_t> elts;
+    std::vector<int> kls, group;
+    std::vector<std::uint64_t *> out;
+    in.reserve(total);
+    for (std::size_t g = 0; g < ops.size(); g++)
+    {
+        const LsOp &o = *ops[g];
+        for (std::size_t i = 0; i < o.in.size(); i++)
+        {
+            if (o.steps[i] == 0) continue;
+            check_ct(context_, *o.in[i], "encrypted");
+            const std::uint32_t e = mhe_galois_elt_from_step(__builtin_ctzll(lv.n), o.steps[i]);
+            std::size_t kl = 0;
+            keys.push_back(o.gk->key_for(GaloisKeys::get_index(e), lv.L, s, kl));
+            kls.push_back((int)kl);
+            elts.push_back(e);
+            group.push_back((int)g);
+        }
+    }
+    for (const LsOp *o : ops)
+        for (std::size_t i = 0; i < o->in.size(); i++)
+            if (o->steps[i] != 0) in.push_back(o->in[i]->store().dev_read(s));
+    for (Ciphertext &r : res) out.push_back(r.store().dev_write(s, !accumulate));
+    chk(mhe_rotate_sum(context_.engine(), (int)in.size(), in.data(), elts.data(), keys.data(), kls.data(), group.data(),
+                       (int)ops.size(), out.data(), accumulate ? 1 : 0, (int)lv.L, s));
+    for (std::size_t g = 0; g < ops.size(); g++)
+    {
+        res[g].scale() = ops[g]->in.back()->scale(); // what the fold leaves: the last term's scale
+        *ops[g]->out[0] = std::move(res[g]);
+    }
+    return true;
+}
+
+void Evaluator::rotate_sum(const std::vector<const Ciphertext *> &encrypted, const std::vector<int> &steps,
+                           const GaloisKeys &galois_keys, Ciphertext &destination) const
+{
+    LsOp op;
+    op.kind = LsOp::ROTSUM;
+    op.in = encrypted;
+    op.steps = steps;
+    op.out = { &destination };
+    op.gk = &galois_keys;
+    if ((tl_ls || fiber_merging()) && lockstep_submit(op)) return;
+    if (encrypted.size() != steps.size() || encrypted.empty())
+        throw std::invalid_argument("encrypted and steps must have the same, nonzero size");
+    for (const Ciphertext *c : encrypted)
+        if (!c) throw std::invalid_argument("null ciphertext");
+    std::vector<LsOp *> one{ &op };
+    if (rotate_sum_merged(one)) return;
+    // one by one: the rotations (batched where rotate_vectors can), then the fold in order
+    std::vector<const Ciphertext *> in;
+    std::vector<int> st;
+    std::vector<Ciphertext> rot(encrypted.size());
+    std::vector<Ciphertext *> out;
+    for (std::size_t i = 0; i < encrypted.size(); i++)
+    {
+        if (steps[i] == 0) continue;
+        in.push_back(encrypted[i]);
+        st.push_back(steps[i]);
+        out.push_back(&rot[i]);
+    }
+    rotate_vectors(in, st, galois_keys, out);
+    Ciphertext sum;
+    for (std::size_t i = 0; i < encrypted.size(); i++)
+    {
+        if (i == 0 && steps[i] != 0)
+            sum = std::move(rot[i]);
+        else if (i == 0)
+            sum = *encrypted[i];
+        else
+            add_inplace_reduced_error(sum, steps[i] != 0 ? rot[i] : *encrypted[i]);
+    }
+    destination = std::move(sum);
 }
 
 void Evaluator::relinearize_inplace_many(const std::vector<Ciphertext *> &encrypted, const RelinKeys &relin_keys) const

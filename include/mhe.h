@@ -143,8 +143,9 @@ int mhe_ctx_set_hoist(mhe_ctx *ctx, int on, int check);
 int mhe_ctx_get_hoist(mhe_ctx *ctx, int *on, int *check);
 int mhe_hoist_stats(mhe_ctx *ctx, uint64_t *rotations, uint64_t *mac_launches, uint64_t *check_mismatches, int reset);
 /* Device scratch the context holds: per-stream workspaces (key-switch / rescale scratch for up to
- * 8 batch entries at the key level), hoisting buffers, Galois negation-mask tables, and the number
- * of streams with a workspace. */
+ * 8 batch entries at the key level, and the group accumulators of mhe_rotate_sum on the streams
+ * that called it), hoisting buffers, Galois negation-mask tables, and the number of streams with a
+ * workspace. */
 int mhe_scratch_bytes(mhe_ctx *ctx, uint64_t *workspace, uint64_t *hoisting, uint64_t *masks, int *streams);
 /* Fault injection for tests: the nth next device allocation of the context (mhe_malloc_async, or a
  * workspace / hoisting scratch growth) fails with MHE_ERR_MEMORY as if the device were out of
@@ -268,6 +269,26 @@ int mhe_apply_galois_to(mhe_ctx *ctx, const uint64_t *in, uint64_t *out, uint32_
 int mhe_apply_galois_batch(mhe_ctx *ctx, int count, const uint64_t *const *in, uint64_t *const *out,
                            const uint32_t *elts, const uint64_t *const *keys, const int *key_limbs, int limbs,
                            void *stream);
+/* Rotate and sum (no SEAL counterpart; the giant-step sums of the BSGS linear transforms,
+ * ckks_bootstrapping/Bootstrapper.cpp:2040-2087):
+ * out[g][2][L][n] = (accumulate ? out[g] : 0) + sum over the entries i of group g of
+ * mhe_apply_galois_to(in[i], elts[i], keys[i]) -- the words of rotating one by one and adding with
+ * mhe_add (add_inplace_reduced_error at equal levels), with one ModDown forward NTT per limb per
+ * group.  group[] is non-decreasing, 0..groups-1, no group empty.  Outputs disjoint from every input
+ * and from each other.
+ * Every rotation keeps its own inverse NTT of the special limb and SEAL's integer lift to each data
+ * prime (evaluator.cpp:2466-2524); what follows the lift is linear mod q_i, so the lifted values and
+ * the key products are summed per group and the forward NTT, the subtraction and the product with
+ * P^-1 run once.  (Special limbs are never added mod P: that would lose the carry.)
+ * All arguments are checked and all scratch is grown before the first launch: a failed call leaves
+ * every out[g] as it was.  The group accumulators are allocated by the first call on a stream (and
+ * grown by the first call at a higher level), so capturing a call into a graph needs one warm call
+ * of that level on the stream first.
+ * mhe_rotsum_stats: groups summed and entries rotated by mhe_rotate_sum since the last reset. */
+int mhe_rotate_sum(mhe_ctx *ctx, int count, const uint64_t *const *in, const uint32_t *elts,
+                   const uint64_t *const *keys, const int *key_limbs, const int *group, int groups,
+                   uint64_t *const *out, int accumulate, int limbs, void *stream);
+int mhe_rotsum_stats(mhe_ctx *ctx, uint64_t *sums, uint64_t *terms, int reset);
 /* mhe_rescale_to_next for each i: in[i][size][L][n] -> out[i][size][L-1][n]. */
 int mhe_rescale_batch(mhe_ctx *ctx, int count, const uint64_t *const *in, uint64_t *const *out, int size, int limbs,
                       void *stream);

@@ -3,6 +3,9 @@
 Times the evaluator's small-level building blocks through the C ABI with HIP events on the engine's
 stream: rescale (1 and 4 ciphertexts per launch), key switch / relinearize (1 and 4), rotations with
 4 distinct keys, forward NTT of one ciphertext, and an HMult.  Prints one JSON line per operation.
+rotaddGxT / rotsumGxT (--rotsum GxT): the giant-step sums of G images, T rotations of distinct inputs
+each with T keys shared over the images -- mhe_apply_galois_batch + T - 1 mhe_add per sum against one
+mhe_rotate_sum.
 Used for A/B runs of library variants (MHE_LIB_PATH=build/var/NAME/libmhe.so).
 
     python scripts/ubench_ops.py [--limbs 31] [--reps 50]
@@ -28,6 +31,7 @@ def main():
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--ops", default="rescale,rescale4,ks,ks4,ks4s,rot4,ntt,hmult")
     ap.add_argument("--bsgs", default="8x7", help="inputs x rotations of the bsgs op (keys shared over inputs)")
+    ap.add_argument("--rotsum", default="1x8", help="sums x rotations per sum of the rotadd / rotsum ops")
     ap.add_argument("--hoist", type=int, default=None, help="hoisted rotations on (1) / off (0); default: the context's")
     a = ap.parse_args()
     log_n, n = 16, 1 << 16
@@ -67,7 +71,27 @@ def main():
         b_k = [bkeys[s] for _ in range(H) for s in range(R)]
         b_out = [eng.empty(2, L, n) for _ in b_in]
 
+    if "rotsum" in a.ops or "rotadd" in a.ops:
+        G, T = (int(x) for x in a.rotsum.split("x"))
+        rkeys = [rnd(L, 2, K, n, limbs=K) for _ in range(T)]
+        for k in rkeys:
+            eng.key_prepare(k)
+        r_in = [rnd(2, L, n, limbs=L) for _ in range(G * T)]
+        r_el = [pow(5, 8 * (t + 1), 2 * n) for _ in range(G) for t in range(T)]
+        r_k = [rkeys[t] for _ in range(G) for t in range(T)]
+        r_grp = [g for g in range(G) for _ in range(T)]
+        r_rot = [eng.empty(2, L, n) for _ in r_in]
+        r_sum = [eng.empty(2, L, n) for _ in range(G)]
+
+    def rotadd():
+        eng.apply_galois_batch(r_in, r_el, r_k, r_rot)
+        for g in range(G):
+            for t in range(1, T):
+                eng.add(r_rot[g * T], r_rot[g * T + t], r_rot[g * T])
+
     ops = {
+        "rotadd": rotadd,
+        "rotsum": lambda: eng.rotate_sum(r_in, r_el, r_k, groups=r_grp, outs=r_sum),
         "rescale": lambda: eng.rescale_to_next(cts[0], outs[0]),
         "rescale4": lambda: eng.rescale_batch(cts[:4], outs[:4]),
         "rescale8": lambda: eng.rescale_batch(cts, outs),
@@ -95,7 +119,8 @@ def main():
         t1.record(st)
         torch.cuda.synchronize()
         us = t0.elapsed_time(t1) * 1000 / a.reps
-        print(json.dumps({"op": name if name != "bsgs" else "bsgs" + a.bsgs, "limbs": L, "us": round(us, 2),
+        label = name + a.bsgs if name == "bsgs" else name + a.rotsum if name in ("rotadd", "rotsum") else name
+        print(json.dumps({"op": label, "limbs": L, "us": round(us, 2),
                           "hoist": int(eng.hoist()[0]), "lib": os.environ.get("MHE_LIB_PATH", "libmhe.so")}),
               flush=True)
 
