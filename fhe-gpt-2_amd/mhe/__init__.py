@@ -113,6 +113,22 @@ SIGNATURES = {
 }
 
 
+LK_ADDSUB, LK_MULPLAIN, LK_MULPLAIN_ADD, LK_SCALAR, LK_TENSOR, LK_COPY = 1, 2, 3, 4, 5, 6  # MHE_LK_*
+OPK_MULPLAIN, OPK_ADDSUB = 3, 4  # MHE_OPK_*
+
+
+class Launch(ctypes.Structure):
+    """mhe_launch (include/mhe.h): the descriptor of one elementwise launch, for Engine.launch_run."""
+    _fields_ = [("kind", ctypes.c_int), ("op", ctypes.c_int),
+                ("a", vp), ("b", vp),
+                ("out", vp),
+                ("polys", ctypes.c_int), ("limbs", ctypes.c_int),
+                ("bytes", ctypes.c_size_t),
+                ("scalars", ctypes.c_uint64 * 64),
+                ("stream", vp),
+                ("rc", ctypes.c_int)]
+
+
 class MheError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"{msg} (code {code})")
@@ -346,6 +362,32 @@ class Engine:
 
     def add_scalar(self, a, scalars, out=None):
         return self._scalar(lib().mhe_add_scalar, a, scalars, out)
+
+    def multiply_plain_add(self, a, pt, acc):
+        """mhe_multiply_plain_add: acc += a * pt (pt broadcast over the polys of a), in one pass."""
+        p, l = self._pl(a)
+        _check(lib().mhe_multiply_plain_add(self._h, _ptr(a), _ptr(pt), _ptr(acc), p, l, self.stream()))
+        return acc
+
+    def set_scalar(self, scalars, polys, limbs, out=None):
+        """mhe_set_scalar: out[p][l][*] = scalars[l] (the NTT form of a constant plaintext)."""
+        out = self.empty(polys, limbs, self.n) if out is None else out
+        s = (ctypes.c_uint64 * limbs)(*[int(x) for x in scalars])
+        _check(lib().mhe_set_scalar(self._h, s, _ptr(out), polys, limbs, self.stream()))
+        return out
+
+    def launch_run(self, descriptors):
+        """mhe_launch_run: run the Launch descriptors, same-shaped ones merged into launches of up to
+        8.  Returns the call's rc (the first failing entry's, 0 if none); each descriptor's rc is set."""
+        arr = (ctypes.POINTER(Launch) * len(descriptors))(*[ctypes.pointer(d) for d in descriptors])
+        return lib().mhe_launch_run(self._h, arr, len(descriptors))
+
+    def op_counts(self, kind, levels=None, reset=False):
+        """mhe_op_counts: counts[l] of `kind` (OPK_*) at l limbs since the last reset."""
+        levels = self.K + 1 if levels is None else levels
+        out = (ctypes.c_uint64 * levels)()
+        _check(lib().mhe_op_counts(self._h, kind, out, levels, 1 if reset else 0))
+        return list(out)
 
     def multiply(self, a, b, out3=None):
         L = a.shape[1]
