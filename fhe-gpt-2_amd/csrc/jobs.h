@@ -1,0 +1,605 @@
+// Job descriptors of the NTT passes (ntt.h): a job maps the launch's job index y to a view -- the
+// source and destination of one limb, its prime and twiddles, and the load / store that fuse the
+// step's arithmetic (lifts, epilogues) into the transform.  Kernel arguments, filled on the host by
+// the pipelines of mhe.hip.
+#pragma once
+
+// A batch of jobs of one kind: entry e owns job indices [e * per, (e + 1) * per) of the launch and
+// its own buffers (pointers inside j[e]); the shared geometry (level, primes) is the same for all.
+template <class Job>
+struct JobB
+{
+    Job j[MHE_MAXB];
+    int per = 1; // jobs per entry
+    __device__ auto view(int y) const
+    {
+        const int e = y / per;
+        return j[e].view(y - e * per);
+    }
+};
+// Plain transform over [poly][limb][n] with limb l on prime l (optionally src != dst).
+struct JobPlain
+{
+    const u64 *src;
+    u64 *dst;
+    const PrimeDev *primes;
+    const Tw *tw;
+    int limbs;
+    int log_n;
+    int mode; // forward row store: 0 = lazy [0,4q), 1 = full; inverse col store: 0 lazy [0,2q), 1 full
+    struct View
+    {
+        const u64 *src;
+        u64 *dst;
+        PrimeDev p;
+        const Tw *tw;
+        int mode;
+        bool skip;
+        __device__ u64 load(u32 x) const { return src[x]; }
+        __device__ void store_fwd(u32 x, u64 v) const
+        {
+            if (mode) v = csub(csub(v, p.two_q), p.q);
+            dst[x] = v;
+        }
+    };
+    __device__ View view(int y) const
+    {
+        const int l = y % limbs;
+        const size_t off = (size_t)y << log_n;
+        return View{ src + off, dst + off, primes[l], tw + ((size_t)l << log_n), mode, false };
+    }
+};
+
+// Views must expose store(); wrappers pick the forward / inverse reduction.
+struct JobFwdPlain : JobPlain
+{
+    struct V2 : View
+    {
+        __device__ void store(u32 x, u64 v) const { store_fwd(x, v); }
+    };
+    __device__ V2 view(int y) const { return V2{ JobPlain::view(y) }; }
+};
+
+struct JobInvPlain : JobPlain
+{
+    struct V2 : View
+    {
+        __device__ void store(u32 x, u64 v) const
+        {
+            if (mode) v = csub(v, p.q);
+            dst[x] = v;
+        }
+    };
+    __device__ V2 view(int y) const { return V2{ JobPlain::view(y) }; }
+};
+
+// Key-switching ModUp, column pass (evaluator.cpp:2386-2408): job y = I*L + J lifts digit J
+// (canonical mod q_J, from INTT(target)) to prime I and starts its NTT; I == L is the special
+// prime.  I == J is skipped: the MAC reads the input NTT form (evaluator.cpp:2380-2384).
+struct JobModUpCol
+{
+    const u64 *coeff; // [L][n]
+    u64 *modup;       // [chunk][L][n] for output primes I0 .. I0+chunk-1
+    const PrimeDev *primes;
+    const Tw *tw;
+    int L, K, log_n, I0;
+    struct View
+    {
+        const u64 *src;
+        u64 *dst;
+        PrimeDev p;
+        const Tw *tw;
+        bool reduce;
+        bool skip;
+        __device__ u64 load(u32 x) const
+        {
+            u64 v = src[x];
+            return reduce ? barrett64(v, p) : v;
+        }
+        __device__ void store(u32 x, u64 v) const { dst[x] = v; }
+    };
+    __device__ View view(int y) const
+    {
+        const int I = I0 + y / L, J = y % L;
+        const int pi = (I == L) ? K - 1 : I;
+        View v;
+        v.src = coeff + ((size_t)J << log_n);
+        v.dst = modup + ((size_t)y << log_n);
+        v.p = prime_at(primes, pi);
+        v.tw = tw + ((size_t)pi << log_n);
+        v.reduce = prime_at(primes, J).q > v.p.q; // key_modulus[J] <= key_modulus[key_index] -> copy
+        v.skip = (I == J);
+        return v;
+    }
+};
+
+struct JobModUpRow
+{
+    u64 *modup;
+    const PrimeDev *primes;
+    const Tw *tw;
+    int L, K, log_n, I0;
+    struct View
+    {
+        u64 *buf;
+        PrimeDev p;
+        const Tw *tw;
+        bool skip;
+        __device__ u64 load(u32 x) const { return buf[x]; }
+        // canonical output keeps the 128-bit MAC safe for any digit count (< 2^8 terms)
+        __device__ void store(u32 x, u64 v) const { buf[x] = csub(csub(v, p.two_q), p.q); }
+    };
+    __device__ View view(int y) const
+    {
+        const int I = I0 + y / L, J = y % L;
+        const int pi = (I == L) ? K - 1 : I;
+        return View{ modup + ((size_t)y << log_n), prime_at(primes, pi), tw + ((size_t)pi << log_n), I == J };
+    }
+};
+
+// The hoisted ModUp's row pass (hoist.h): src [I][J][n] column-pass output -> dst the same layout,
+// canonical, each 256-slot block stored in bit-reversed order.  BREV (n = 2^16, 256-slot rows): the
+// row pass reads its LDS row bit-reversed and stores contiguously; otherwise the store scatters
+// inside the block (out of place: at n < 2^16 a block spans rows of several workgroups).
+template <bool BREV>
+struct JobModUpRowH
+{
+    const u64 *src;
+    u64 *dst;
+    const PrimeDev *primes;
+    const Tw *tw;
+    int L, K, log_n;
+    struct View
+    {
+        const u64 *src;
+        u64 *dst;
+        PrimeDev p;
+        const Tw *tw;
+        bool skip;
+        static constexpr bool brev = BREV;
+        __device__ u64 load(u32 x) const { return src[x]; }
+        __device__ void store(u32 x, u64 v) const
+        {
+            dst[BREV ? x : ((x & ~255u) | brev8(x & 255u))] = csub(csub(v, p.two_q), p.q);
+        }
+    };
+    __device__ View view(int y) const
+    {
+        const int I = y / L, J = y % L;
+        const int pi = (I == L) ? K - 1 : I;
+        const size_t off = (size_t)y << log_n;
+        return View{ src + off, dst + off, prime_at(primes, pi), tw + ((size_t)pi << log_n), I == J };
+    }
+};
+
+// Key-switching ModDown (evaluator.cpp:2466-2524).  t_last = INTT_lazy(acc[k][L]) in [0,2P);
+// column pass job y = k*L + i computes ((barrett(t_last + P/2) mod q_i) + fix_i) and starts
+// the NTT mod q_i; the row pass epilogue does ct[k][i] += (acc[k][i] + 4q_i - t) * P^-1.
+struct JobModDownCol
+{
+    const u64 *acc; // [2][L+1][n]
+    u64 *scratch;   // [2][L][n]
+    const PrimeDev *primes;
+    const Tw *tw;
+    int L, K, log_n;
+    int fixed_i = -1; // >= 0: one job per poly, all on limb fixed_i
+    struct View
+    {
+        const u64 *src;
+        u64 *dst;
+        PrimeDev p;
+        PrimeDev P;
+        const Tw *tw;
+        u64 half, fix;
+        bool reduce;
+        bool skip;
+        __device__ u64 lift(u64 s) const
+        {
+            u64 t = barrett64(s + half, P);
+            if (reduce) t = barrett64(t, p);
+            return t + fix;
+        }
+        // the integer lift() stands for, from s canonical mod P: s - P when s > P/2, else s
+        __device__ double lift_c(u64 s) const { return fp_from_u52(s) - (s > half ? (double)P.q : 0.0); }
+        __device__ u64 load(u32 x) const { return lift(src[x]); }
+        __device__ void store(u32 x, u64 v) const { dst[x] = v; }
+    };
+    __device__ View view(int y) const
+    {
+        const int k = fixed_i >= 0 ? y : y / L, i = fixed_i >= 0 ? fixed_i : y % L;
+        View v;
+        v.src = acc + ((size_t)(k * (L + 1) + L) << log_n);
+        v.dst = scratch + ((size_t)y << log_n);
+        v.p = prime_at(primes, i);
+        v.P = prime_at(primes, K - 1);
+        v.tw = tw + ((size_t)i << log_n);
+        v.half = v.P.q >> 1;
+        v.fix = v.p.q - barrett64(v.half, v.p);
+        v.reduce = v.P.q > v.p.q;
+        v.skip = false;
+        return v;
+    }
+};
+
+struct JobModDownRow
+{
+    u64 *scratch;
+    const u64 *acc;
+    u64 *ct; // [2][L][n]
+    const PrimeDev *primes;
+    const Tw *tw;
+    const Tw *invq; // [K][K]
+    int L, K, log_n;
+    int fixed_i = -1; // >= 0: one job per poly, all on limb fixed_i
+    int c1_write = 0; // 1: ct[1] = ModDown(acc[1]) instead of += (apply_galois: ct[1] was 0)
+    int fp = 0;       // every prime < 2^51: the epilogue in exact FP64 (fparith.h)
+    struct View
+    {
+        u64 *buf;
+        const u64 *accp;
+        u64 *ctp;
+        PrimeDev p;
+        const Tw *tw;
+        Tw inv;
+        bool skip;
+        bool replace;
+        bool fp;
+        double pd, pi, invd;
+        __device__ u64 load(u32 x) const { return buf[x]; }
+        struct Pre
+        {
+            u64 a, c;
+        };
+        __device__ Pre pre(u32 x) const { return Pre{ accp[x], replace ? 0 : ctp[x] }; }
+        __device__ void store(u32 x, u64 t, Pre o) const
+        {
+            if (fp)
+            {
+                // acc and t canonical: (acc - t) P^-1 in (-1.25p, 1.25p), plus c < p, one
+                // canonicalisation (|.| < 2^53): the residue of the integer form
+                const double v = fp_mulmod_gen(fp_from_u52(o.a) - fp_from_u52(t), invd, pd, pi);
+                ctp[x] = fp_canon(replace ? v : v + fp_from_u52(o.c), pd, pi);
+                return;
+            }
+            u64 v = mul_shoup(o.a + p.four_q - t, inv.x, inv.y, p.q);
+            ctp[x] = replace ? v : addmod(v, o.c, p.q); // 0 + v = v: the same word
+        }
+        __device__ void store(u32 x, u64 t) const { store(x, t, pre(x)); }
+    };
+    __device__ View view(int y) const
+    {
+        const int k = fixed_i >= 0 ? y : y / L, i = fixed_i >= 0 ? fixed_i : y % L;
+        View v;
+        v.buf = scratch + ((size_t)y << log_n);
+        v.accp = acc + ((size_t)(k * (L + 1) + i) << log_n);
+        v.ctp = ct + ((size_t)(k * L + i) << log_n);
+        v.p = prime_at(primes, i);
+        v.tw = tw + ((size_t)i << log_n);
+        v.inv = tw_at(invq, (size_t)(K - 1) * K + i);
+        v.skip = false;
+        v.replace = c1_write && k == 1;
+        v.fp = fp != 0;
+        v.pd = (double)v.p.q;
+        v.pi = 1.0 / v.pd;
+        v.invd = (double)v.inv.x;
+        return v;
+    }
+};
+
+// Rescale (util/rns.cpp:737-808): last[s] = INTT(in[s][L-1]) canonical; column pass job
+// y = s*(L-1) + i: ((last + half mod q_last) mod q_i) + (q_i - half mod q_i); row pass
+// epilogue out[s][i] = (in[s][i] + 4q_i - t) * q_last^-1 mod q_i.
+struct JobRescaleCol
+{
+    const u64 *last; // [size][n]
+    u64 *scratch;    // [size][L-1][n]
+    const PrimeDev *primes;
+    const Tw *tw;
+    int L, log_n;
+    struct View
+    {
+        const u64 *src;
+        u64 *dst;
+        PrimeDev p;
+        u64 ql, half, neg_half;
+        const Tw *tw;
+        bool reduce;
+        bool skip;
+        __device__ u64 lift(u64 s) const // s canonical mod q_last
+        {
+            u64 v = csub(s + half, ql);
+            if (reduce) v = barrett64(v, p);
+            return v + neg_half;
+        }
+        // the integer lift() stands for: s - q_last when s > q_last/2, else s
+        __device__ double lift_c(u64 s) const { return fp_from_u52(s) - (s > half ? (double)ql : 0.0); }
+        __device__ u64 load(u32 x) const { return lift(src[x]); }
+        __device__ void store(u32 x, u64 v) const { dst[x] = v; }
+    };
+    __device__ View view(int y) const
+    {
+        const int s = y / (L - 1), i = y % (L - 1);
+        View v;
+        v.src = last + ((size_t)s << log_n);
+        v.dst = scratch + ((size_t)y << log_n);
+        v.p = prime_at(primes, i);
+        v.ql = prime_at(primes, L - 1).q;
+        v.half = v.ql >> 1;
+        v.neg_half = v.p.q - barrett64(v.half, v.p);
+        v.tw = tw + ((size_t)i << log_n);
+        v.reduce = v.p.q < v.ql;
+        v.skip = false;
+        return v;
+    }
+};
+
+struct JobRescaleRow
+{
+    u64 *scratch;
+    const u64 *in; // [size][L][n]
+    u64 *out;      // [size][L-1][n]
+    const PrimeDev *primes;
+    const Tw *tw;
+    const Tw *invq;
+    int L, K, log_n;
+    int fp = 0; // every prime < 2^51: the epilogue in exact FP64 (fparith.h)
+    struct View
+    {
+        u64 *buf;
+        const u64 *inp;
+        u64 *outp;
+        PrimeDev p;
+        const Tw *tw;
+        Tw inv;
+        bool skip, fp;
+        double pd, pi, invd;
+        __device__ u64 load(u32 x) const { return buf[x]; }
+        using Pre = u64;
+        __device__ Pre pre(u32 x) const { return inp[x]; }
+        __device__ void store(u32 x, u64 t, u64 in) const
+        {
+            if (fp) // in and t canonical: (in - t) q_last^-1 in (-1.25p, 1.25p), canonicalised
+                outp[x] = fp_canon(fp_mulmod_gen(fp_from_u52(in) - fp_from_u52(t), invd, pd, pi), pd, pi);
+            else
+                outp[x] = mul_shoup(in + p.four_q - t, inv.x, inv.y, p.q);
+        }
+        __device__ void store(u32 x, u64 t) const { store(x, t, pre(x)); }
+    };
+    __device__ View view(int y) const
+    {
+        const int s = y / (L - 1), i = y % (L - 1);
+        View v;
+        v.buf = scratch + ((size_t)y << log_n);
+        v.inp = in + ((size_t)(s * L + i) << log_n);
+        v.outp = out + ((size_t)(s * (L - 1) + i) << log_n);
+        v.p = prime_at(primes, i);
+        v.tw = tw + ((size_t)i << log_n);
+        v.inv = tw_at(invq, (size_t)(L - 1) * K + i);
+        v.skip = false;
+        v.fp = fp != 0;
+        v.pd = (double)v.p.q;
+        v.pi = 1.0 / v.pd;
+        v.invd = (double)v.inv.x;
+        return v;
+    }
+};
+
+// ModDown fused with the following rescale (one HMult = multiply + relinearize + rescale).
+// With t_i the ModDown lift of INTT(acc_P) and r_i the rescale lift of last = INTT(ct'_{L-1})
+// (ct' = ct after ModDown), SEAL computes
+//     out_i = ((c_i + (acc_i + 4q - NTT(t_i)) P^-1) + 4q - NTT(r_i)) q_{L-1}^-1   (mod q_i),
+// and NTT is linear mod q_i, so the same residues come from ONE forward NTT per limb:
+//     out_i = (c_i + acc_i P^-1 - NTT(t_i P^-1 + r_i)) q_{L-1}^-1.
+// Column pass job y = k*(L-1) + i builds u_i = t_i P^-1 + r_i (evaluator.cpp:2466-2524 and
+// util/rns.cpp:737-808 lifts), the row pass epilogue forms out_i.
+struct JobMDRCol
+{
+    const u64 *acc;  // [2][L+1][n], limb L = INTT_lazy(acc_P) in [0, 2P)
+    const u64 *last; // [2][n] = INTT(ct'[k][L-1]), canonical
+    u64 *scratch;    // [2][L-1][n]
+    const PrimeDev *primes;
+    const Tw *tw;
+    const Tw *invq; // [K][K]
+    int L, K, log_n;
+    int fp = 0; // every prime < 2^51 (NttMode::fp): the lift in exact FP64 (fparith.h)
+    struct View
+    {
+        const u64 *accP, *lastp;
+        u64 *dst;
+        PrimeDev p, P;
+        const Tw *tw;
+        Tw pinv;
+        u64 halfP, fixP, ql, halfL, neg_halfL;
+        bool redP, redL, skip, fp;
+        double pd, pi, pinvd;
+        __device__ u64 load(u32 x) const
+        {
+            if (fp)
+            {
+                // accP in [0, 2P) -> a mod P canonical by two conditional subtractions; t + fixP
+                // and the rescale lift r + neg_halfL are exact doubles (< 2^52), the product by
+                // P^-1 is in (-2p, 2p), the sum below 2^53: one canonicalisation, the same residue
+                const u64 t = csub(csub(accP[x] + halfP, 2 * P.q), P.q);
+                const u64 r = csub(lastp[x] + halfL, ql);
+                const double u = fp_mulmod_gen(fp_from_u52(t + fixP), pinvd, pd, pi) + fp_from_u52(r + neg_halfL);
+                return fp_canon(u, pd, pi);
+            }
+            u64 t = barrett64(accP[x] + halfP, P);
+            if (redP) t = barrett64(t, p);
+            t += fixP;                                  // ModDown lift, [0, 2q)
+            u64 r = csub(lastp[x] + halfL, ql);
+            if (redL) r = barrett64(r, p);
+            r += neg_halfL;                             // rescale lift, [0, 2q)
+            const u64 u = mul_shoup(t, pinv.x, pinv.y, p.q) + r; // [0, 3q)
+            return csub(csub(u, p.two_q), p.q);
+        }
+        __device__ void store(u32 x, u64 v) const { dst[x] = v; }
+        // k_col_lift2 (FP): the two lifts' centred integers, the same for every output prime -- the
+        // special accumulator limb (in [0, 2P)) and the rescale's last limb (canonical mod q_last)
+        __device__ void src_c(u32 x, double &ct, double &cr) const
+        {
+            const u64 a = csub(accP[x], P.q), l = lastp[x];
+            ct = fp_from_u52(a) - (a > halfP ? (double)P.q : 0.0);
+            cr = fp_from_u52(l) - (l > halfL ? (double)ql : 0.0);
+        }
+        // t P^-1 + r mod p from them: |.| < 1.25p + 2^50, congruent to load()'s value
+        __device__ double lift_f(double ct, double cr) const { return fp_mulmod_gen(ct, pinvd, pd, pi) + cr; }
+    };
+    __device__ View view(int y) const
+    {
+        const int k = y / (L - 1), i = y % (L - 1);
+        View v;
+        v.accP = acc + ((size_t)(k * (L + 1) + L) << log_n);
+        v.lastp = last + ((size_t)k << log_n);
+        v.dst = scratch + ((size_t)y << log_n);
+        v.p = prime_at(primes, i);
+        v.P = prime_at(primes, K - 1);
+        v.tw = tw + ((size_t)i << log_n);
+        v.pinv = tw_at(invq, (size_t)(K - 1) * K + i);
+        v.halfP = v.P.q >> 1;
+        v.fixP = v.p.q - barrett64(v.halfP, v.p);
+        v.redP = v.P.q > v.p.q;
+        v.ql = prime_at(primes, L - 1).q;
+        v.halfL = v.ql >> 1;
+        v.neg_halfL = v.p.q - barrett64(v.halfL, v.p);
+        v.redL = v.p.q < v.ql;
+        v.skip = false;
+        v.fp = fp != 0;
+        v.pd = (double)v.p.q;
+        v.pi = 1.0 / v.pd;
+        v.pinvd = (double)v.pinv.x;
+        return v;
+    }
+};
+
+struct JobMDRRow
+{
+    u64 *scratch;
+    const u64 *acc; // [2][L+1][n]
+    const u64 *ct;  // [2][L][n], limbs < L-1 before ModDown
+    u64 *out;       // [2][L-1][n]
+    const PrimeDev *primes;
+    const Tw *tw;
+    const Tw *invq;
+    int L, K, log_n;
+    int fp = 0; // every prime < 2^51: the epilogue in exact FP64 (fparith.h)
+    struct View
+    {
+        u64 *buf;
+        const u64 *accp, *ctp;
+        u64 *outp;
+        PrimeDev p;
+        const Tw *tw;
+        Tw pinv, qlinv;
+        bool skip, fp;
+        double pd, pi, pinvd, qlinvd;
+        __device__ u64 load(u32 x) const { return buf[x]; }
+        struct Pre
+        {
+            u64 a, c;
+        };
+        __device__ Pre pre(u32 x) const { return Pre{ accp[x], ctp[x] }; }
+        __device__ void store(u32 x, u64 U, Pre o) const
+        {
+            if (fp)
+            {
+                // acc_i P^-1 in (-1.25p, 1.25p); c + a - U is an exact integer below 2^53; its
+                // centered residue times q_{L-1}^-1, canonicalised: the residue of the integer form
+                const double a = fp_mulmod_gen(fp_from_u52(o.a), pinvd, pd, pi);
+                const double v = fp_reduce(fp_from_u52(o.c) + a - fp_from_u52(U), pd, pi);
+                outp[x] = fp_canon(fp_mulmod_gen(v, qlinvd, pd, pi), pd, pi);
+                return;
+            }
+            const u64 a = mul_shoup(o.a, pinv.x, pinv.y, p.q); // acc_i P^-1
+            const u64 v = o.c + a + p.four_q - U;              // < 6q
+            outp[x] = mul_shoup(v, qlinv.x, qlinv.y, p.q);
+        }
+        __device__ void store(u32 x, u64 U) const { store(x, U, pre(x)); }
+    };
+    __device__ View view(int y) const
+    {
+        const int k = y / (L - 1), i = y % (L - 1);
+        View v;
+        v.buf = scratch + ((size_t)y << log_n);
+        v.accp = acc + ((size_t)(k * (L + 1) + i) << log_n);
+        v.ctp = ct + ((size_t)(k * L + i) << log_n);
+        v.outp = out + ((size_t)(k * (L - 1) + i) << log_n);
+        v.p = prime_at(primes, i);
+        v.tw = tw + ((size_t)i << log_n);
+        v.pinv = tw_at(invq, (size_t)(K - 1) * K + i);
+        v.qlinv = tw_at(invq, (size_t)(L - 1) * K + i);
+        v.skip = false;
+        v.fp = fp != 0;
+        v.pd = (double)v.p.q;
+        v.pi = 1.0 / v.pd;
+        v.pinvd = (double)v.pinv.x;
+        v.qlinvd = (double)v.qlinv.x;
+        return v;
+    }
+};
+
+// Rescale INTT of the last limb: src limb (L-1) of poly s -> last[s], canonical.
+struct JobLastInv
+{
+    const u64 *in;
+    u64 *last;
+    const PrimeDev *primes;
+    const Tw *itw;
+    int L, log_n;
+    int lazy;
+    struct View
+    {
+        const u64 *src;
+        u64 *dst;
+        PrimeDev p;
+        const Tw *tw;
+        int lazy;
+        bool skip;
+        __device__ u64 load(u32 x) const { return src[x]; }
+        __device__ void store(u32 x, u64 v) const { dst[x] = lazy ? v : csub(v, p.q); }
+    };
+    __device__ View view(int y) const
+    {
+        View v;
+        v.src = in + ((size_t)(y * L + (L - 1)) << log_n);
+        v.dst = last + ((size_t)y << log_n);
+        v.p = prime_at(primes, L - 1);
+        v.tw = itw + ((size_t)(L - 1) << log_n);
+        v.lazy = lazy;
+        v.skip = false;
+        return v;
+    }
+};
+
+// Generic job on explicit (src, dst, prime) with a per-job stride: used for the key-switch
+// INTT of the target (limb J on prime J) and of the special accumulator limbs.
+struct JobStrided
+{
+    const u64 *src;
+    u64 *dst;
+    size_t src_stride, dst_stride; // in words, per job
+    int prime0;                    // prime index of job 0
+    int prime_step;                // 0: all jobs on prime0; 1: job y on prime0 + y
+    const PrimeDev *primes;
+    const Tw *tw;
+    int log_n;
+    int mode; // inverse store: 0 lazy, 1 full
+    const int *run_if = nullptr; // non-null: every job returns unless *run_if != 0 (hoist.h fallback)
+    struct View
+    {
+        const u64 *src;
+        u64 *dst;
+        PrimeDev p;
+        const Tw *tw;
+        int mode;
+        bool skip;
+        __device__ u64 load(u32 x) const { return src[x]; }
+        __device__ void store(u32 x, u64 v) const { dst[x] = mode ? csub(v, p.q) : v; }
+    };
+    __device__ View view(int y) const
+    {
+        const int pi = prime0 + prime_step * y;
+        return View{ src + y * src_stride, dst + y * dst_stride, primes[pi], tw + ((size_t)pi << log_n), mode,
+                     run_if && !*run_if };
+    }
+};

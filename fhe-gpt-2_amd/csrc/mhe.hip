@@ -8,6 +8,10 @@
 //                                                          inv_root_powers_, bit-reversed index
 //   invq[K][K]       (q_j^-1 mod q_i, Shoup)            -- RNSTool::inv_q_last_mod_q for every j
 // Scratch workspaces are per stream (see Workspace).
+//
+// This file holds the context, the pipelines and the C ABI; it is the one translation unit of
+// mhe.o and includes the NTT (ntt.h), hoisting (hoist.h), job descriptors (jobs.h), elementwise
+// kernels (elem.h) and the device allocator (devalloc.h) once each.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,6 +29,9 @@
 #include "arith.h"
 #include "ntt.h"
 #include "hoist.h"
+#include "jobs.h"
+#include "elem.h"
+#include "devalloc.h"
 
 #define MHE_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -173,11 +180,28 @@ struct WsEntry
     u64 *ct3 = nullptr;   // [3][L][n]     tensor output of a batched HMult
 };
 
+// One grow-on-demand device buffer of a stream's scratch.  p and the growth are guarded by the
+// workspace's lock; bytes is read by mhe_scratch_bytes without it.
+struct Scratch
+{
+    u64 *p = nullptr;
+    std::atomic<size_t> bytes{ 0 };
+    // Replaces the buffer by one of nbytes, draining st first (its queued kernels may still use the
+    // old one); consults mhe_debug_fail_alloc.  On failure the buffer is empty.
+    int grow(mhe_ctx *c, hipStream_t st, size_t nbytes);
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+};
+
 struct Workspace
 {
     int max_limbs = 0;
     int entries = 0;      // batch entries the scratch is sized for (<= MHE_MAXB)
-    u64 *base = nullptr;
+    Scratch base;
     WsEntry e[MHE_MAXB];
     u64 *coeff = nullptr; // entry 0's buffers under their old names
     u64 *modup = nullptr;
@@ -186,23 +210,39 @@ struct Workspace
     u64 *ct3 = nullptr;   // [3][L][n]     tensor output for hmult
     // hoisted rotations (hoist.h): the ModUp of up to MHE_MAXB inputs, [K][K-1][n] each, and one
     // zero-coefficient flag per input
-    u64 *hoist_base = nullptr;
+    Scratch hoist_base;
     int hoist_entries = 0;
+    int hoist_limbs = 0; // the hoisting buffers' level (per-input ModUp of up to this many limbs)
     u64 *hoist[MHE_MAXB] = {};
     u64 *hacc[MHE_MAXB * MHE_HOIST_R] = {}; // [2][K][n] key products of each hoisted rotation
     int *flags = nullptr;
     // mhe_rotate_sum: per group in flight (MHE_MAXB) the sum of the key products A [2][L+1][n] and the
     // sum of the lifted special limbs T [2][L][n], L = rs_limbs; allocated by the first call
-    u64 *rs_base = nullptr;
+    Scratch rs_base;
     int rs_limbs = 0;
     // kernel timing (mhe_ctx_set_timing): event pairs recorded around the two dominant
     // key-switch kernels on this stream, read back by mhe_kernel_time
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[2];
     size_t ev_used[2] = { 0, 0 };
-    // device bytes of base / hoist_base / rs_base: written under mu, read by mhe_scratch_bytes without it
-    std::atomic<size_t> bytes{ 0 }, hoist_bytes{ 0 }, rs_bytes{ 0 };
-    int hoist_limbs = 0;                // the hoisting buffers' level (per-input ModUp of up to this many limbs)
-    std::mutex mu;                      // growth of this stream's buffers
+    std::mutex mu; // growth of this stream's buffers
+    // frees everything the stream owns on the device (the caller has drained the stream)
+    void release()
+    {
+        base.release();
+        hoist_base.release();
+        rs_base.release();
+        if (flags) (void)hipFree(flags);
+        flags = nullptr;
+        for (auto &v : ev)
+        {
+            for (auto &e : v)
+            {
+                (void)hipEventDestroy(e.first);
+                (void)hipEventDestroy(e.second);
+            }
+            v.clear();
+        }
+    }
 };
 
 enum TimedKernel
@@ -312,13 +352,9 @@ static void timing_end(hipEvent_t *pair, hipStream_t st)
 }
 
 // Scratch allocation (hipMalloc) that, when the device reports out of memory, first gives the
-// blocks the engine's caching allocator holds back to the device (mhe_internal_release_cached:
+// blocks the engine's caching allocator holds back to the device (devalloc.h release_cached_blocks:
 // synchronises the device) and retries once.  Freed ciphertext / key buffers stay cached for reuse at
 // their own sizes; a plain hipMalloc cannot use them.
-static void release_cached_blocks();
-// process-wide counts for mhe_alloc_stats: allocations that succeeded only after the cache was
-// released, and allocations that failed (including injected ones)
-static std::atomic<unsigned long long> g_alloc_retries{ 0 }, g_alloc_failures{ 0 };
 static hipError_t scratch_alloc(void **p, size_t bytes)
 {
     hipError_t e = hipMalloc(p, bytes);
@@ -349,6 +385,25 @@ static bool injected_alloc_failure(mhe_ctx *c)
     return false;
 }
 
+int Scratch::grow(mhe_ctx *c, hipStream_t st, size_t nbytes)
+{
+    HIP_TRY(hipSetDevice(c->device));
+    if (p)
+    {
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipFree(p));
+    }
+    p = nullptr;
+    bytes = 0;
+    if (injected_alloc_failure(c) || scratch_alloc((void **)&p, nbytes) != hipSuccess)
+    {
+        p = nullptr;
+        return fail(MHE_ERR_MEMORY, "workspace allocation failed");
+    }
+    bytes = nbytes;
+    return MHE_OK;
+}
+
 // The scratch of stream st, for ciphertexts of up to `limbs` limbs and `entries` batch entries.
 // The context lock only guards the map; growing one stream's scratch (which drains that stream
 // first: its queued kernels may still use the old buffers) holds that workspace's own lock, so
@@ -365,30 +420,18 @@ static int get_ws(mhe_ctx *c, hipStream_t st, int limbs, Workspace **out, int en
     std::lock_guard<std::mutex> g(w.mu);
     if (w.max_limbs < limbs || w.entries < entries)
     {
-        if (w.base)
-        {
-            HIP_TRY(hipStreamSynchronize(st));
-            HIP_TRY(hipFree(w.base));
-        }
-        w.base = nullptr;
-        w.bytes = 0;
         const int E = std::max(entries, w.entries);
         const size_t n = c->n, L = std::max(limbs, w.max_limbs);
         const size_t Lc = L < 3 ? 3 : L;
         const size_t per = Lc * n + (L + 1) * L * n + 2 * (L + 1) * n + 3 * L * n;
         size_t words = (size_t)E * per + L * n;
-        HIP_TRY(hipSetDevice(c->device));
-        if (injected_alloc_failure(c) || scratch_alloc((void **)&w.base, words * sizeof(u64)) != hipSuccess)
-        {
-            w.base = nullptr;
-            w.max_limbs = 0;
-            w.entries = 0;
-            return fail(MHE_ERR_MEMORY, "workspace allocation failed");
-        }
-        w.bytes = words * sizeof(u64);
+        w.max_limbs = 0;
+        w.entries = 0;
+        int r = w.base.grow(c, st, words * sizeof(u64));
+        if (r) return r;
         for (int i = 0; i < E; i++)
         {
-            w.e[i].coeff = w.base + (size_t)i * per;
+            w.e[i].coeff = w.base.p + (size_t)i * per;
             w.e[i].modup = w.e[i].coeff + Lc * n;
             w.e[i].acc = w.e[i].modup + (L + 1) * L * n;
             w.e[i].ct3 = w.e[i].acc + 2 * (L + 1) * n;
@@ -396,7 +439,7 @@ static int get_ws(mhe_ctx *c, hipStream_t st, int limbs, Workspace **out, int en
         w.coeff = w.e[0].coeff;
         w.modup = w.e[0].modup;
         w.acc = w.e[0].acc;
-        w.tmp = w.base + (size_t)E * per;
+        w.tmp = w.base.p + (size_t)E * per;
         w.ct3 = w.e[0].ct3;
         w.max_limbs = (int)L;
         w.entries = E;
@@ -405,898 +448,252 @@ static int get_ws(mhe_ctx *c, hipStream_t st, int limbs, Workspace **out, int en
     return MHE_OK;
 }
 
-// ================================================================================ jobs
-// A batch of jobs of one kind: entry e owns job indices [e * per, (e + 1) * per) of the launch and
-// its own buffers (pointers inside j[e]); the shared geometry (level, primes) is the same for all.
-template <class Job>
-struct JobB
+// ======================================================================= dispatch helpers
+static bool valid_ctx(mhe_ctx *c)
 {
-    Job j[MHE_MAXB];
-    int per = 1; // jobs per entry
-    __device__ auto view(int y) const
-    {
-        const int e = y / per;
-        return j[e].view(y - e * per);
-    }
-};
-// Plain transform over [poly][limb][n] with limb l on prime l (optionally src != dst).
-struct JobPlain
-{
-    const u64 *src;
-    u64 *dst;
-    const PrimeDev *primes;
-    const Tw *tw;
-    int limbs;
-    int log_n;
-    int mode; // forward row store: 0 = lazy [0,4q), 1 = full; inverse col store: 0 lazy [0,2q), 1 full
-    struct View
-    {
-        const u64 *src;
-        u64 *dst;
-        PrimeDev p;
-        const Tw *tw;
-        int mode;
-        bool skip;
-        __device__ u64 load(u32 x) const { return src[x]; }
-        __device__ void store_fwd(u32 x, u64 v) const
-        {
-            if (mode) v = csub(csub(v, p.two_q), p.q);
-            dst[x] = v;
-        }
-    };
-    __device__ View view(int y) const
-    {
-        const int l = y % limbs;
-        const size_t off = (size_t)y << log_n;
-        return View{ src + off, dst + off, primes[l], tw + ((size_t)l << log_n), mode, false };
-    }
-};
-
-// Views must expose store(); wrappers pick the forward / inverse reduction.
-struct JobFwdPlain : JobPlain
-{
-    struct V2 : View
-    {
-        __device__ void store(u32 x, u64 v) const { store_fwd(x, v); }
-    };
-    __device__ V2 view(int y) const { return V2{ JobPlain::view(y) }; }
-};
-
-struct JobInvPlain : JobPlain
-{
-    struct V2 : View
-    {
-        __device__ void store(u32 x, u64 v) const
-        {
-            if (mode) v = csub(v, p.q);
-            dst[x] = v;
-        }
-    };
-    __device__ V2 view(int y) const { return V2{ JobPlain::view(y) }; }
-};
-
-// Key-switching ModUp, column pass (evaluator.cpp:2386-2408): job y = I*L + J lifts digit J
-// (canonical mod q_J, from INTT(target)) to prime I and starts its NTT; I == L is the special
-// prime.  I == J is skipped: the MAC reads the input NTT form (evaluator.cpp:2380-2384).
-struct JobModUpCol
-{
-    const u64 *coeff; // [L][n]
-    u64 *modup;       // [chunk][L][n] for output primes I0 .. I0+chunk-1
-    const PrimeDev *primes;
-    const Tw *tw;
-    int L, K, log_n, I0;
-    struct View
-    {
-        const u64 *src;
-        u64 *dst;
-        PrimeDev p;
-        const Tw *tw;
-        bool reduce;
-        bool skip;
-        __device__ u64 load(u32 x) const
-        {
-            u64 v = src[x];
-            return reduce ? barrett64(v, p) : v;
-        }
-        __device__ void store(u32 x, u64 v) const { dst[x] = v; }
-    };
-    __device__ View view(int y) const
-    {
-        const int I = I0 + y / L, J = y % L;
-        const int pi = (I == L) ? K - 1 : I;
-        View v;
-        v.src = coeff + ((size_t)J << log_n);
-        v.dst = modup + ((size_t)y << log_n);
-        v.p = prime_at(primes, pi);
-        v.tw = tw + ((size_t)pi << log_n);
-        v.reduce = prime_at(primes, J).q > v.p.q; // key_modulus[J] <= key_modulus[key_index] -> copy
-        v.skip = (I == J);
-        return v;
-    }
-};
-
-struct JobModUpRow
-{
-    u64 *modup;
-    const PrimeDev *primes;
-    const Tw *tw;
-    int L, K, log_n, I0;
-    struct View
-    {
-        u64 *buf;
-        PrimeDev p;
-        const Tw *tw;
-        bool skip;
-        __device__ u64 load(u32 x) const { return buf[x]; }
-        // canonical output keeps the 128-bit MAC safe for any digit count (< 2^8 terms)
-        __device__ void store(u32 x, u64 v) const { buf[x] = csub(csub(v, p.two_q), p.q); }
-    };
-    __device__ View view(int y) const
-    {
-        const int I = I0 + y / L, J = y % L;
-        const int pi = (I == L) ? K - 1 : I;
-        return View{ modup + ((size_t)y << log_n), prime_at(primes, pi), tw + ((size_t)pi << log_n), I == J };
-    }
-};
-
-// The hoisted ModUp's row pass (hoist.h): src [I][J][n] column-pass output -> dst the same layout,
-// canonical, each 256-slot block stored in bit-reversed order.  BREV (n = 2^16, 256-slot rows): the
-// row pass reads its LDS row bit-reversed and stores contiguously; otherwise the store scatters
-// inside the block (out of place: at n < 2^16 a block spans rows of several workgroups).
-template <bool BREV>
-struct JobModUpRowH
-{
-    const u64 *src;
-    u64 *dst;
-    const PrimeDev *primes;
-    const Tw *tw;
-    int L, K, log_n;
-    struct View
-    {
-        const u64 *src;
-        u64 *dst;
-        PrimeDev p;
-        const Tw *tw;
-        bool skip;
-        static constexpr bool brev = BREV;
-        __device__ u64 load(u32 x) const { return src[x]; }
-        __device__ void store(u32 x, u64 v) const
-        {
-            dst[BREV ? x : ((x & ~255u) | brev8(x & 255u))] = csub(csub(v, p.two_q), p.q);
-        }
-    };
-    __device__ View view(int y) const
-    {
-        const int I = y / L, J = y % L;
-        const int pi = (I == L) ? K - 1 : I;
-        const size_t off = (size_t)y << log_n;
-        return View{ src + off, dst + off, prime_at(primes, pi), tw + ((size_t)pi << log_n), I == J };
-    }
-};
-
-// Key-switching ModDown (evaluator.cpp:2466-2524).  t_last = INTT_lazy(acc[k][L]) in [0,2P);
-// column pass job y = k*L + i computes ((barrett(t_last + P/2) mod q_i) + fix_i) and starts
-// the NTT mod q_i; the row pass epilogue does ct[k][i] += (acc[k][i] + 4q_i - t) * P^-1.
-struct JobModDownCol
-{
-    const u64 *acc; // [2][L+1][n]
-    u64 *scratch;   // [2][L][n]
-    const PrimeDev *primes;
-    const Tw *tw;
-    int L, K, log_n;
-    int fixed_i = -1; // >= 0: one job per poly, all on limb fixed_i
-    struct View
-    {
-        const u64 *src;
-        u64 *dst;
-        PrimeDev p;
-        PrimeDev P;
-        const Tw *tw;
-        u64 half, fix;
-        bool reduce;
-        bool skip;
-        __device__ u64 lift(u64 s) const
-        {
-            u64 t = barrett64(s + half, P);
-            if (reduce) t = barrett64(t, p);
-            return t + fix;
-        }
-        // the integer lift() stands for, from s canonical mod P: s - P when s > P/2, else s
-        __device__ double lift_c(u64 s) const { return fp_from_u52(s) - (s > half ? (double)P.q : 0.0); }
-        __device__ u64 load(u32 x) const { return lift(src[x]); }
-        __device__ void store(u32 x, u64 v) const { dst[x] = v; }
-    };
-    __device__ View view(int y) const
-    {
-        const int k = fixed_i >= 0 ? y : y / L, i = fixed_i >= 0 ? fixed_i : y % L;
-        View v;
-        v.src = acc + ((size_t)(k * (L + 1) + L) << log_n);
-        v.dst = scratch + ((size_t)y << log_n);
-        v.p = prime_at(primes, i);
-        v.P = prime_at(primes, K - 1);
-        v.tw = tw + ((size_t)i << log_n);
-        v.half = v.P.q >> 1;
-        v.fix = v.p.q - barrett64(v.half, v.p);
-        v.reduce = v.P.q > v.p.q;
-        v.skip = false;
-        return v;
-    }
-};
-
-struct JobModDownRow
-{
-    u64 *scratch;
-    const u64 *acc;
-    u64 *ct; // [2][L][n]
-    const PrimeDev *primes;
-    const Tw *tw;
-    const Tw *invq; // [K][K]
-    int L, K, log_n;
-    int fixed_i = -1; // >= 0: one job per poly, all on limb fixed_i
-    int c1_write = 0; // 1: ct[1] = ModDown(acc[1]) instead of += (apply_galois: ct[1] was 0)
-    int fp = 0;       // every prime < 2^51: the epilogue in exact FP64 (fparith.h)
-    struct View
-    {
-        u64 *buf;
-        const u64 *accp;
-        u64 *ctp;
-        PrimeDev p;
-        const Tw *tw;
-        Tw inv;
-        bool skip;
-        bool replace;
-        bool fp;
-        double pd, pi, invd;
-        __device__ u64 load(u32 x) const { return buf[x]; }
-        struct Pre
-        {
-            u64 a, c;
-        };
-        __device__ Pre pre(u32 x) const { return Pre{ accp[x], replace ? 0 : ctp[x] }; }
-        __device__ void store(u32 x, u64 t, Pre o) const
-        {
-            if (fp)
-            {
-                // acc and t canonical: (acc - t) P^-1 in (-1.25p, 1.25p), plus c < p, one
-                // canonicalisation (|.| < 2^53): the residue of the integer form
-                const double v = fp_mulmod_gen(fp_from_u52(o.a) - fp_from_u52(t), invd, pd, pi);
-                ctp[x] = fp_canon(replace ? v : v + fp_from_u52(o.c), pd, pi);
-                return;
-            }
-            u64 v = mul_shoup(o.a + p.four_q - t, inv.x, inv.y, p.q);
-            ctp[x] = replace ? v : addmod(v, o.c, p.q); // 0 + v = v: the same word
-        }
-        __device__ void store(u32 x, u64 t) const { store(x, t, pre(x)); }
-    };
-    __device__ View view(int y) const
-    {
-        const int k = fixed_i >= 0 ? y : y / L, i = fixed_i >= 0 ? fixed_i : y % L;
-        View v;
-        v.buf = scratch + ((size_t)y << log_n);
-        v.accp = acc + ((size_t)(k * (L + 1) + i) << log_n);
-        v.ctp = ct + ((size_t)(k * L + i) << log_n);
-        v.p = prime_at(primes, i);
-        v.tw = tw + ((size_t)i << log_n);
-        v.inv = tw_at(invq, (size_t)(K - 1) * K + i);
-        v.skip = false;
-        v.replace = c1_write && k == 1;
-        v.fp = fp != 0;
-        v.pd = (double)v.p.q;
-        v.pi = 1.0 / v.pd;
-        v.invd = (double)v.inv.x;
-        return v;
-    }
-};
-
-// Rescale (util/rns.cpp:737-808): last[s] = INTT(in[s][L-1]) canonical; column pass job
-// y = s*(L-1) + i: ((last + half mod q_last) mod q_i) + (q_i - half mod q_i); row pass
-// epilogue out[s][i] = (in[s][i] + 4q_i - t) * q_last^-1 mod q_i.
-struct JobRescaleCol
-{
-    const u64 *last; // [size][n]
-    u64 *scratch;    // [size][L-1][n]
-    const PrimeDev *primes;
-    const Tw *tw;
-    int L, log_n;
-    struct View
-    {
-        const u64 *src;
-        u64 *dst;
-        PrimeDev p;
-        u64 ql, half, neg_half;
-        const Tw *tw;
-        bool reduce;
-        bool skip;
-        __device__ u64 lift(u64 s) const // s canonical mod q_last
-        {
-            u64 v = csub(s + half, ql);
-            if (reduce) v = barrett64(v, p);
-            return v + neg_half;
-        }
-        // the integer lift() stands for: s - q_last when s > q_last/2, else s
-        __device__ double lift_c(u64 s) const { return fp_from_u52(s) - (s > half ? (double)ql : 0.0); }
-        __device__ u64 load(u32 x) const { return lift(src[x]); }
-        __device__ void store(u32 x, u64 v) const { dst[x] = v; }
-    };
-    __device__ View view(int y) const
-    {
-        const int s = y / (L - 1), i = y % (L - 1);
-        View v;
-        v.src = last + ((size_t)s << log_n);
-        v.dst = scratch + ((size_t)y << log_n);
-        v.p = prime_at(primes, i);
-        v.ql = prime_at(primes, L - 1).q;
-        v.half = v.ql >> 1;
-        v.neg_half = v.p.q - barrett64(v.half, v.p);
-        v.tw = tw + ((size_t)i << log_n);
-        v.reduce = v.p.q < v.ql;
-        v.skip = false;
-        return v;
-    }
-};
-
-struct JobRescaleRow
-{
-    u64 *scratch;
-    const u64 *in; // [size][L][n]
-    u64 *out;      // [size][L-1][n]
-    const PrimeDev *primes;
-    const Tw *tw;
-    const Tw *invq;
-    int L, K, log_n;
-    int fp = 0; // every prime < 2^51: the epilogue in exact FP64 (fparith.h)
-    struct View
-    {
-        u64 *buf;
-        const u64 *inp;
-        u64 *outp;
-        PrimeDev p;
-        const Tw *tw;
-        Tw inv;
-        bool skip, fp;
-        double pd, pi, invd;
-        __device__ u64 load(u32 x) const { return buf[x]; }
-        using Pre = u64;
-        __device__ Pre pre(u32 x) const { return inp[x]; }
-        __device__ void store(u32 x, u64 t, u64 in) const
-        {
-            if (fp) // in and t canonical: (in - t) q_last^-1 in (-1.25p, 1.25p), canonicalised
-                outp[x] = fp_canon(fp_mulmod_gen(fp_from_u52(in) - fp_from_u52(t), invd, pd, pi), pd, pi);
-            else
-                outp[x] = mul_shoup(in + p.four_q - t, inv.x, inv.y, p.q);
-        }
-        __device__ void store(u32 x, u64 t) const { store(x, t, pre(x)); }
-    };
-    __device__ View view(int y) const
-    {
-        const int s = y / (L - 1), i = y % (L - 1);
-        View v;
-        v.buf = scratch + ((size_t)y << log_n);
-        v.inp = in + ((size_t)(s * L + i) << log_n);
-        v.outp = out + ((size_t)(s * (L - 1) + i) << log_n);
-        v.p = prime_at(primes, i);
-        v.tw = tw + ((size_t)i << log_n);
-        v.inv = tw_at(invq, (size_t)(L - 1) * K + i);
-        v.skip = false;
-        v.fp = fp != 0;
-        v.pd = (double)v.p.q;
-        v.pi = 1.0 / v.pd;
-        v.invd = (double)v.inv.x;
-        return v;
-    }
-};
-
-// ModDown fused with the following rescale (one HMult = multiply + relinearize + rescale).
-// With t_i the ModDown lift of INTT(acc_P) and r_i the rescale lift of last = INTT(ct'_{L-1})
-// (ct' = ct after ModDown), SEAL computes
-//     out_i = ((c_i + (acc_i + 4q - NTT(t_i)) P^-1) + 4q - NTT(r_i)) q_{L-1}^-1   (mod q_i),
-// and NTT is linear mod q_i, so the same residues come from ONE forward NTT per limb:
-//     out_i = (c_i + acc_i P^-1 - NTT(t_i P^-1 + r_i)) q_{L-1}^-1.
-// Column pass job y = k*(L-1) + i builds u_i = t_i P^-1 + r_i (evaluator.cpp:2466-2524 and
-// util/rns.cpp:737-808 lifts), the row pass epilogue forms out_i.
-struct JobMDRCol
-{
-    const u64 *acc;  // [2][L+1][n], limb L = INTT_lazy(acc_P) in [0, 2P)
-    const u64 *last; // [2][n] = INTT(ct'[k][L-1]), canonical
-    u64 *scratch;    // [2][L-1][n]
-    const PrimeDev *primes;
-    const Tw *tw;
-    const Tw *invq; // [K][K]
-    int L, K, log_n;
-    int fp = 0; // every prime < 2^51 (NttMode::fp): the lift in exact FP64 (fparith.h)
-    struct View
-    {
-        const u64 *accP, *lastp;
-        u64 *dst;
-        PrimeDev p, P;
-        const Tw *tw;
-        Tw pinv;
-        u64 halfP, fixP, ql, halfL, neg_halfL;
-        bool redP, redL, skip, fp;
-        double pd, pi, pinvd;
-        __device__ u64 load(u32 x) const
-        {
-            if (fp)
-            {
-                // accP in [0, 2P) -> a mod P canonical by two conditional subtractions; t + fixP
-                // and the rescale lift r + neg_halfL are exact doubles (< 2^52), the product by
-                // P^-1 is in (-2p, 2p), the sum below 2^53: one canonicalisation, the same residue
-                const u64 t = csub(csub(accP[x] + halfP, 2 * P.q), P.q);
-                const u64 r = csub(lastp[x] + halfL, ql);
-                const double u = fp_mulmod_gen(fp_from_u52(t + fixP), pinvd, pd, pi) + fp_from_u52(r + neg_halfL);
-                return fp_canon(u, pd, pi);
-            }
-            u64 t = barrett64(accP[x] + halfP, P);
-            if (redP) t = barrett64(t, p);
-            t += fixP;                                  // ModDown lift, [0, 2q)
-            u64 r = csub(lastp[x] + halfL, ql);
-            if (redL) r = barrett64(r, p);
-            r += neg_halfL;                             // rescale lift, [0, 2q)
-            const u64 u = mul_shoup(t, pinv.x, pinv.y, p.q) + r; // [0, 3q)
-            return csub(csub(u, p.two_q), p.q);
-        }
-        __device__ void store(u32 x, u64 v) const { dst[x] = v; }
-        // k_col_lift2 (FP): the two lifts' centred integers, the same for every output prime -- the
-        // special accumulator limb (in [0, 2P)) and the rescale's last limb (canonical mod q_last)
-        __device__ void src_c(u32 x, double &ct, double &cr) const
-        {
-            const u64 a = csub(accP[x], P.q), l = lastp[x];
-            ct = fp_from_u52(a) - (a > halfP ? (double)P.q : 0.0);
-            cr = fp_from_u52(l) - (l > halfL ? (double)ql : 0.0);
-        }
-        // t P^-1 + r mod p from them: |.| < 1.25p + 2^50, congruent to load()'s value
-        __device__ double lift_f(double ct, double cr) const { return fp_mulmod_gen(ct, pinvd, pd, pi) + cr; }
-    };
-    __device__ View view(int y) const
-    {
-        const int k = y / (L - 1), i = y % (L - 1);
-        View v;
-        v.accP = acc + ((size_t)(k * (L + 1) + L) << log_n);
-        v.lastp = last + ((size_t)k << log_n);
-        v.dst = scratch + ((size_t)y << log_n);
-        v.p = prime_at(primes, i);
-        v.P = prime_at(primes, K - 1);
-        v.tw = tw + ((size_t)i << log_n);
-        v.pinv = tw_at(invq, (size_t)(K - 1) * K + i);
-        v.halfP = v.P.q >> 1;
-        v.fixP = v.p.q - barrett64(v.halfP, v.p);
-        v.redP = v.P.q > v.p.q;
-        v.ql = prime_at(primes, L - 1).q;
-        v.halfL = v.ql >> 1;
-        v.neg_halfL = v.p.q - barrett64(v.halfL, v.p);
-        v.redL = v.p.q < v.ql;
-        v.skip = false;
-        v.fp = fp != 0;
-        v.pd = (double)v.p.q;
-        v.pi = 1.0 / v.pd;
-        v.pinvd = (double)v.pinv.x;
-        return v;
-    }
-};
-
-struct JobMDRRow
-{
-    u64 *scratch;
-    const u64 *acc; // [2][L+1][n]
-    const u64 *ct;  // [2][L][n], limbs < L-1 before ModDown
-    u64 *out;       // [2][L-1][n]
-    const PrimeDev *primes;
-    const Tw *tw;
-    const Tw *invq;
-    int L, K, log_n;
-    int fp = 0; // every prime < 2^51: the epilogue in exact FP64 (fparith.h)
-    struct View
-    {
-        u64 *buf;
-        const u64 *accp, *ctp;
-        u64 *outp;
-        PrimeDev p;
-        const Tw *tw;
-        Tw pinv, qlinv;
-        bool skip, fp;
-        double pd, pi, pinvd, qlinvd;
-        __device__ u64 load(u32 x) const { return buf[x]; }
-        struct Pre
-        {
-            u64 a, c;
-        };
-        __device__ Pre pre(u32 x) const { return Pre{ accp[x], ctp[x] }; }
-        __device__ void store(u32 x, u64 U, Pre o) const
-        {
-            if (fp)
-            {
-                // acc_i P^-1 in (-1.25p, 1.25p); c + a - U is an exact integer below 2^53; its
-                // centered residue times q_{L-1}^-1, canonicalised: the residue of the integer form
-                const double a = fp_mulmod_gen(fp_from_u52(o.a), pinvd, pd, pi);
-                const double v = fp_reduce(fp_from_u52(o.c) + a - fp_from_u52(U), pd, pi);
-                outp[x] = fp_canon(fp_mulmod_gen(v, qlinvd, pd, pi), pd, pi);
-                return;
-            }
-            const u64 a = mul_shoup(o.a, pinv.x, pinv.y, p.q); // acc_i P^-1
-            const u64 v = o.c + a + p.four_q - U;              // < 6q
-            outp[x] = mul_shoup(v, qlinv.x, qlinv.y, p.q);
-        }
-        __device__ void store(u32 x, u64 U) const { store(x, U, pre(x)); }
-    };
-    __device__ View view(int y) const
-    {
-        const int k = y / (L - 1), i = y % (L - 1);
-        View v;
-        v.buf = scratch + ((size_t)y << log_n);
-        v.accp = acc + ((size_t)(k * (L + 1) + i) << log_n);
-        v.ctp = ct + ((size_t)(k * L + i) << log_n);
-        v.outp = out + ((size_t)(k * (L - 1) + i) << log_n);
-        v.p = prime_at(primes, i);
-        v.tw = tw + ((size_t)i << log_n);
-        v.pinv = tw_at(invq, (size_t)(K - 1) * K + i);
-        v.qlinv = tw_at(invq, (size_t)(L - 1) * K + i);
-        v.skip = false;
-        v.fp = fp != 0;
-        v.pd = (double)v.p.q;
-        v.pi = 1.0 / v.pd;
-        v.pinvd = (double)v.pinv.x;
-        v.qlinvd = (double)v.qlinv.x;
-        return v;
-    }
-};
-
-// Rescale INTT of the last limb: src limb (L-1) of poly s -> last[s], canonical.
-struct JobLastInv
-{
-    const u64 *in;
-    u64 *last;
-    const PrimeDev *primes;
-    const Tw *itw;
-    int L, log_n;
-    int lazy;
-    struct View
-    {
-        const u64 *src;
-        u64 *dst;
-        PrimeDev p;
-        const Tw *tw;
-        int lazy;
-        bool skip;
-        __device__ u64 load(u32 x) const { return src[x]; }
-        __device__ void store(u32 x, u64 v) const { dst[x] = lazy ? v : csub(v, p.q); }
-    };
-    __device__ View view(int y) const
-    {
-        View v;
-        v.src = in + ((size_t)(y * L + (L - 1)) << log_n);
-        v.dst = last + ((size_t)y << log_n);
-        v.p = prime_at(primes, L - 1);
-        v.tw = itw + ((size_t)(L - 1) << log_n);
-        v.lazy = lazy;
-        v.skip = false;
-        return v;
-    }
-};
-
-// Generic job on explicit (src, dst, prime) with a per-job stride: used for the key-switch
-// INTT of the target (limb J on prime J) and of the special accumulator limbs.
-struct JobStrided
-{
-    const u64 *src;
-    u64 *dst;
-    size_t src_stride, dst_stride; // in words, per job
-    int prime0;                    // prime index of job 0
-    int prime_step;                // 0: all jobs on prime0; 1: job y on prime0 + y
-    const PrimeDev *primes;
-    const Tw *tw;
-    int log_n;
-    int mode; // inverse store: 0 lazy, 1 full
-    const int *run_if = nullptr; // non-null: every job returns unless *run_if != 0 (hoist.h fallback)
-    struct View
-    {
-        const u64 *src;
-        u64 *dst;
-        PrimeDev p;
-        const Tw *tw;
-        int mode;
-        bool skip;
-        __device__ u64 load(u32 x) const { return src[x]; }
-        __device__ void store(u32 x, u64 v) const { dst[x] = mode ? csub(v, p.q) : v; }
-    };
-    __device__ View view(int y) const
-    {
-        const int pi = prime0 + prime_step * y;
-        return View{ src + y * src_stride, dst + y * dst_stride, primes[pi], tw + ((size_t)pi << log_n), mode,
-                     run_if && !*run_if };
-    }
-};
-
-// ============================================================================ kernels
-// Elementwise kernels process 2 residues per lane (16-B loads); n is a multiple of 512.
-#define ELEM_GRID(total2) dim3((unsigned)(((total2) + 255) / 256))
-
-// Elementwise products in FP64 (csrc/fparith.h) for primes below 2^51, where the integer path's
-// 64 x 64 -> 128-bit product and Barrett reduction cost several half- and quarter-rate instructions:
-// canonical residues are exact doubles, fp_mulmod_gen leaves a*b mod q in (-1.25q, 1.25q) and
-// fp_canon returns the canonical residue, so the words are the integer path's.  fp: the context's
-// FP64 mode (MHE_FP=0 keeps every product on the integer path).
-__device__ __forceinline__ bool elem_fp(int fp, const PrimeDev &p)
-{
-    return fp && p.q < (1ull << 51);
-}
-__device__ __forceinline__ double mulmod_fd(u64 a, u64 b, const PrimeDev &p) // (-1.25q, 1.25q)
-{
-    return fp_mulmod_gen(fp_from_u52(a), fp_from_u52(b), p.qd, p.qi);
-}
-__device__ __forceinline__ u64 mulmod_e(u64 a, u64 b, const PrimeDev &p, bool f)
-{
-    return f ? fp_canon(mulmod_fd(a, b, p), p.qd, p.qi) : mulmod(a, b, p);
+    return c && c->primes;
 }
 
-__device__ __forceinline__ void addsub_at(const u64 *a, const u64 *b, u64 *out, const PrimeDev *primes, int limbs,
-                                          int log_n, size_t i2, int op)
+static hipStream_t S(void *s)
 {
-    const size_t i = i2 * 2;
-    const int l = (int)((i >> log_n) % limbs);
-    const u64 q = primes[l].q;
-    ulonglong2 x = *(const ulonglong2 *)(a + i);
-    ulonglong2 r;
-    if (op == 0)
+    return (hipStream_t)s;
+}
+
+static int check_limbs(mhe_ctx *c, int limbs, int lo)
+{
+    if (!valid_ctx(c)) return fail(MHE_ERR_ARG, "context is not valid");
+    if (limbs < lo || limbs > c->K - 1) return fail(MHE_ERR_ARG, "encrypted is not valid for encryption parameters");
+    return MHE_OK;
+}
+
+// Do the word ranges [a, a + aw) and [b, b + bw) share a word?  The batched entry points run every
+// entry inside the same kernels, so an output that overlaps another entry's operand would be read
+// and written by one launch in an order that depends on the grid (not the order of count calls).
+static bool ranges_overlap(const u64 *a, size_t aw, const u64 *b, size_t bw)
+{
+    return a < b + bw && b < a + aw;
+}
+
+static void count_op(mhe_ctx *c, int kind, int L, unsigned long long k)
+{
+    if (kind >= 0 && kind < MHE_OPK_KINDS && L >= 0 && L < MHE_OPK_LEVELS) c->opc[kind][L].fetch_add(k, std::memory_order_relaxed);
+}
+
+static int check_poly_args(mhe_ctx *c, const void *a, int polys, int limbs)
+{
+    if (!valid_ctx(c)) return fail(MHE_ERR_ARG, "context is not valid");
+    if (!a || polys < 1 || limbs < 1 || limbs > c->K) return fail(MHE_ERR_ARG, "invalid polynomial arguments");
+    return MHE_OK;
+}
+
+// MHE_ALLOC_TRACE: the operand p of the calling entry point, [polys][limbs][n] words.  Nothing is
+// read through c unless it is valid, and nothing at all when tracing is off.
+static void trace_operand(const char *fn, mhe_ctx *c, const char *what, const void *p, size_t polys, size_t limbs)
+{
+    if (trace_on() && valid_ctx(c)) trace_range(fn, what, p, (polys * limbs) << c->log_n);
+}
+#define TR(what, p, polys, limbs) trace_operand(__func__, c, what, p, (size_t)(polys), (size_t)(limbs))
+
+// ------------------------------------------------------------------- elementwise launches
+// The unit of work of the elementwise family and the d2d copy is the mhe_launch descriptor
+// (include/mhe.h).  An entry point fills one and hands it to elem_entry: elem_check validates it,
+// the calling thread's hook (mhe_set_launch_hook) may take it, otherwise elem_launch runs it as a
+// group of one.  mhe_launch_run runs groups of same-shaped descriptors through the same functions.
+static thread_local mhe_launch_hook tl_hook = nullptr;
+static thread_local void *tl_hook_user = nullptr;
+
+static mhe_launch elem_desc(int kind, int op, const u64 *a, const u64 *b, u64 *out, int polys, int limbs, void *stream)
+{
+    mhe_launch l{};
+    l.kind = kind;
+    l.op = op;
+    l.a = a;
+    l.b = b;
+    l.out = out;
+    l.polys = polys;
+    l.limbs = limbs;
+    l.stream = stream;
+    return l;
+}
+
+// The argument checks of the descriptor's entry point, with its return code and message.
+static int elem_check(mhe_ctx *c, const mhe_launch &l)
+{
+    bool b_used = true;
+    switch (l.kind)
     {
-        ulonglong2 y = *(const ulonglong2 *)(b + i);
-        r.x = addmod(x.x, y.x, q);
-        r.y = addmod(x.y, y.y, q);
+    case MHE_LK_COPY: return valid_ctx(c) ? MHE_OK : fail(MHE_ERR_ARG, "invalid argument");
+    case MHE_LK_ADDSUB: b_used = l.op < 2; break; // negate
+    case MHE_LK_MULPLAIN:
+    case MHE_LK_MULPLAIN_ADD: break;
+    case MHE_LK_SCALAR: b_used = false; break;
+    case MHE_LK_TENSOR: b_used = !l.op; break; // square
+    default: return fail(MHE_ERR_ARG, "unknown launch kind");
     }
-    else if (op == 1)
+    const bool set = l.kind == MHE_LK_SCALAR && l.op == 2; // a unused: out stands in for it
+    int r = check_poly_args(c, set ? l.out : l.a, l.kind == MHE_LK_TENSOR ? 2 : l.polys, l.limbs);
+    if (r) return r;
+    if (!l.out || (b_used && !l.b)) return fail(MHE_ERR_ARG, "invalid polynomial arguments");
+    if (l.kind == MHE_LK_SCALAR)
+        for (int i = 0; i < l.limbs; i++)
+            if (l.scalars[i] >= c->q[i]) return fail(MHE_ERR_ARG, "scalar must be less than modulus");
+    return MHE_OK;
+}
+
+// Op counts of B descriptors of l's shape (a tensor product counts once, the others per poly).
+static void elem_count(mhe_ctx *c, const mhe_launch &l, int B)
+{
+    if (l.kind == MHE_LK_COPY) return;
+    const int opk = l.kind == MHE_LK_ADDSUB ? MHE_OPK_ADDSUB
+                    : l.kind == MHE_LK_SCALAR ? MHE_OPK_SCALAR
+                    : l.kind == MHE_LK_TENSOR ? MHE_OPK_TENSOR
+                                              : MHE_OPK_MULPLAIN;
+    const unsigned long long k = (unsigned long long)B * (l.kind == MHE_LK_TENSOR ? 1 : l.polys);
+    count_op(c, opk, l.limbs, k);
+    if (l.kind == MHE_LK_MULPLAIN_ADD) count_op(c, MHE_OPK_ADDSUB, l.limbs, k);
+}
+
+static void scalar_tab(mhe_ctx *c, const mhe_launch &l, ScalarTab &t)
+{
+    for (int i = 0; i < l.limbs; i++)
     {
-        ulonglong2 y = *(const ulonglong2 *)(b + i);
-        r.x = submod(x.x, y.x, q);
-        r.y = submod(x.y, y.y, q);
+        t.v[i] = l.scalars[i];
+        t.vq[i] = host::shoup(l.scalars[i], c->q[i]);
     }
+}
+
+// Can B > 1 descriptors of one shape run as one batched launch?  Copies move 16 bytes per lane.
+static bool elem_batchable(mhe_launch *const *g, int B)
+{
+    if (g[0]->kind != MHE_LK_COPY) return true;
+    uintptr_t bits = g[0]->bytes;
+    for (int k = 0; k < B; k++) bits |= (uintptr_t)g[k]->a | (uintptr_t)g[k]->out;
+    return (bits & 15) == 0;
+}
+
+// Counts and launches a group of B <= MHE_MAXB checked descriptors of one shape (same_shape; B > 1:
+// elem_batchable): one descriptor by the kernel of its kind, several by k_elem_b / k_copy16_b.
+static int elem_launch(mhe_ctx *c, mhe_launch *const *g, int B)
+{
+    const mhe_launch &l = *g[0];
+    const hipStream_t st = S(l.stream);
+    const int log_n = c->log_n, fp = c->nm.fp ? 1 : 0;
+    // a tensor product covers one pair of 2-poly ciphertexts ([limbs] residues per output poly)
+    const size_t total2 = ((size_t)(l.kind == MHE_LK_TENSOR ? 1 : l.polys) * l.limbs << log_n) / 2;
+    const dim3 grid = ELEM_GRID(total2), block(256);
+    elem_count(c, l, B);
+    if (B == 1)
+        switch (l.kind)
+        {
+        case MHE_LK_ADDSUB:
+            hipLaunchKernelGGL(k_addsub, grid, block, 0, st, l.a, l.b, l.out, c->primes, l.limbs, log_n, total2, l.op);
+            break;
+        case MHE_LK_MULPLAIN:
+            hipLaunchKernelGGL(k_mulplain, grid, block, 0, st, l.a, l.b, l.out, c->primes, l.limbs, log_n, total2, fp);
+            break;
+        case MHE_LK_MULPLAIN_ADD:
+            hipLaunchKernelGGL(k_mulplain_add, grid, block, 0, st, l.a, l.b, l.out, c->primes, l.limbs, log_n, total2, fp);
+            break;
+        case MHE_LK_SCALAR:
+        {
+            ScalarTab t;
+            scalar_tab(c, l, t);
+            hipLaunchKernelGGL(k_scalar, grid, block, 0, st, l.a, l.out, c->primes, t, l.limbs, log_n, total2, l.op);
+            break;
+        }
+        case MHE_LK_TENSOR:
+            hipLaunchKernelGGL(k_tensor, grid, block, 0, st, l.a, l.op ? l.a : l.b, l.out, c->primes, l.limbs, log_n,
+                               total2, l.op ? 1 : 0, fp);
+            break;
+        case MHE_LK_COPY:
+        {
+            void *dst = l.out, *stream = l.stream;
+            const void *src = l.a;
+            const size_t bytes = l.bytes;
+            HIP_TRY(mhe_internal_copy_d2d(dst, src, bytes, S(stream)));
+            return MHE_OK;
+        }
+        }
     else
     {
-        r.x = x.x ? q - x.x : 0;
-        r.y = x.y ? q - x.y : 0;
-    }
-    *(ulonglong2 *)(out + i) = r;
-}
-
-__global__ void k_addsub(const u64 *a, const u64 *b, u64 *out, const PrimeDev *primes, int limbs, int log_n,
-                         size_t total2, int op)
-{
-    size_t i2 = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i2 < total2) addsub_at(a, b, out, primes, limbs, log_n, i2, op);
-}
-
-// dyadic product with b broadcast over polys (multiply_plain_ntt)
-__device__ __forceinline__ void mulplain_at(const u64 *a, const u64 *b, u64 *out, const PrimeDev *primes, int limbs,
-                                            int log_n, size_t i2, int fp)
-{
-    const size_t i = i2 * 2;
-    const size_t limb_words = (size_t)limbs << log_n;
-    const int l = (int)((i >> log_n) % limbs);
-    const PrimeDev p = primes[l];
-    const bool f = elem_fp(fp, p); // uniform: a wave's residues are of one limb
-    ulonglong2 x = *(const ulonglong2 *)(a + i);
-    ulonglong2 y = *(const ulonglong2 *)(b + i % limb_words);
-    ulonglong2 r;
-    r.x = mulmod_e(x.x, y.x, p, f);
-    r.y = mulmod_e(x.y, y.y, p, f);
-    *(ulonglong2 *)(out + i) = r;
-}
-
-__global__ void k_mulplain(const u64 *a, const u64 *b, u64 *out, const PrimeDev *primes, int limbs, int log_n,
-                           size_t total2, int fp)
-{
-    size_t i2 = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i2 < total2) mulplain_at(a, b, out, primes, limbs, log_n, i2, fp);
-}
-
-// acc += a * b, b broadcast over polys (multiply_plain_ntt then add_inplace, one pass)
-__device__ __forceinline__ void mulplain_add_at(const u64 *a, const u64 *b, u64 *acc, const PrimeDev *primes,
-                                                int limbs, int log_n, size_t i2, int fp)
-{
-    const size_t i = i2 * 2;
-    const size_t limb_words = (size_t)limbs << log_n;
-    const int l = (int)((i >> log_n) % limbs);
-    const PrimeDev p = primes[l];
-    ulonglong2 x = *(const ulonglong2 *)(a + i);
-    ulonglong2 y = *(const ulonglong2 *)(b + i % limb_words);
-    ulonglong2 z = *(const ulonglong2 *)(acc + i);
-    ulonglong2 r;
-    if (elem_fp(fp, p))
-    {
-        // canonical acc (< q) + a product in (-1.25q, 1.25q): |.| < 2.25q, exact
-        r.x = fp_canon(fp_from_u52(z.x) + mulmod_fd(x.x, y.x, p), p.qd, p.qi);
-        r.y = fp_canon(fp_from_u52(z.y) + mulmod_fd(x.y, y.y, p), p.qd, p.qi);
-    }
-    else
-    {
-        r.x = addmod(z.x, mulmod(x.x, y.x, p), p.q);
-        r.y = addmod(z.y, mulmod(x.y, y.y, p), p.q);
-    }
-    *(ulonglong2 *)(acc + i) = r;
-}
-
-__global__ void k_mulplain_add(const u64 *a, const u64 *b, u64 *acc, const PrimeDev *primes, int limbs, int log_n,
-                               size_t total2, int fp)
-{
-    size_t i2 = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i2 < total2) mulplain_add_at(a, b, acc, primes, limbs, log_n, i2, fp);
-}
-
-// acc = (accumulate ? acc : 0) + sum_k a_k * b_k, up to 16 terms per launch (pointers in the kernel
-// arguments); each thread's 2 * cnt loads are independent, so they are all in flight together
-#define MHE_SUM_TERMS 16
-struct SumPtrs
-{
-    const u64 *a[MHE_SUM_TERMS];
-    const u64 *b[MHE_SUM_TERMS];
-};
-__global__ void k_mulplain_sum(SumPtrs P, int cnt, u64 *acc, int accumulate, const PrimeDev *primes, int limbs,
-                               int log_n, size_t total2, int fp)
-{
-    size_t i2 = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i2 >= total2) return;
-    const size_t i = i2 * 2;
-    const size_t limb_words = (size_t)limbs << log_n;
-    const int l = (int)((i >> log_n) % limbs);
-    const PrimeDev p = primes[l];
-    ulonglong2 z = accumulate ? *(const ulonglong2 *)(acc + i) : ulonglong2{ 0, 0 };
-    if (elem_fp(fp, p))
-    {
-        // FP64 sums: products in (-1.25q, 1.25q), centred by fp_reduce after every second one, so
-        // |sum| < q/2 + 1 + 2.5q < 2^53 throughout; one fp_canon at the end
-        double sx = fp_from_u52(z.x), sy = fp_from_u52(z.y);
-        for (int k = 0; k < cnt; k++)
+        ElemPtrs P{};
+        for (int k = 0; k < B; k++)
         {
-            const ulonglong2 x = *(const ulonglong2 *)(P.a[k] + i);
-            const ulonglong2 y = *(const ulonglong2 *)(P.b[k] + i % limb_words);
-            sx += mulmod_fd(x.x, y.x, p);
-            sy += mulmod_fd(x.y, y.y, p);
-            if (k & 1)
-            {
-                sx = fp_reduce(sx, p.qd, p.qi);
-                sy = fp_reduce(sy, p.qd, p.qi);
-            }
+            P.a[k] = g[k]->a;
+            P.b[k] = g[k]->b;
+            P.out[k] = g[k]->out;
         }
-        z.x = fp_canon(sx, p.qd, p.qi);
-        z.y = fp_canon(sy, p.qd, p.qi);
-    }
-    else
-    {
-        for (int k = 0; k < cnt; k++)
+        if (l.kind == MHE_LK_COPY)
         {
-            const ulonglong2 x = *(const ulonglong2 *)(P.a[k] + i);
-            const ulonglong2 y = *(const ulonglong2 *)(P.b[k] + i % limb_words);
-            z.x = addmod(z.x, mulmod(x.x, y.x, p), p.q);
-            z.y = addmod(z.y, mulmod(x.y, y.y, p), p.q);
+            const size_t cnt = l.bytes / 16;
+            if (!cnt) return MHE_OK;
+            const unsigned cgrid = (unsigned)std::min<size_t>((cnt + 255) / 256, 4096);
+            hipLaunchKernelGGL(k_copy16_b, dim3(cgrid, (unsigned)B), block, 0, st, P, cnt);
+        }
+        else
+        {
+            ScalarTab t{};
+            if (l.kind == MHE_LK_SCALAR) scalar_tab(c, l, t);
+            hipLaunchKernelGGL(k_elem_b, dim3(grid.x, (unsigned)B), block, 0, st, P, c->primes, t, l.limbs, log_n, total2,
+                               l.kind, l.op, fp);
         }
     }
-    *(ulonglong2 *)(acc + i) = z;
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MHE_ERR_DEVICE, std::string(B == 1 ? "kernel launch: " : "") + hipGetErrorString(e));
+    return MHE_OK;
 }
 
-struct ScalarTab
+static int elem_entry(mhe_ctx *c, mhe_launch &l)
 {
-    u64 v[64];
-    u64 vq[64];
-};
-
-__device__ __forceinline__ void scalar_at(const u64 *a, u64 *out, const PrimeDev *primes, const ScalarTab &s, int limbs,
-                                          int log_n, size_t i2, int op)
-{
-    const size_t i = i2 * 2;
-    const int l = (int)((i >> log_n) % limbs);
-    const u64 q = primes[l].q;
-    ulonglong2 r;
-    if (op == 2)
+    int r = elem_check(c, l);
+    if (r) return r;
+    if (tl_hook)
     {
-        r.x = r.y = s.v[l];
-        *(ulonglong2 *)(out + i) = r;
-        return;
+        l.rc = -1;
+        tl_hook(c, &l, tl_hook_user); // gets it run (mhe_launch_run) and sets l.rc
+        return l.rc;
     }
-    ulonglong2 x = *(const ulonglong2 *)(a + i);
-    if (op == 0)
-    {
-        r.x = mul_shoup(x.x, s.v[l], s.vq[l], q);
-        r.y = mul_shoup(x.y, s.v[l], s.vq[l], q);
-    }
-    else
-    {
-        r.x = addmod(x.x, s.v[l], q);
-        r.y = addmod(x.y, s.v[l], q);
-    }
-    *(ulonglong2 *)(out + i) = r;
+    mhe_launch *g = &l;
+    return elem_launch(c, &g, 1);
 }
 
-__global__ void k_scalar(const u64 *a, u64 *out, const PrimeDev *primes, ScalarTab s, int limbs, int log_n,
-                         size_t total2, int op)
+// ----------------------------------------------------------------------------- job builders
+// Plain transform of [polys][limbs][n] on the context's tables (limb l on prime l).
+static JobFwdPlain fwd_plain(mhe_ctx *c, const u64 *src, u64 *dst, int limbs, int mode)
 {
-    size_t i2 = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i2 < total2) scalar_at(a, out, primes, s, limbs, log_n, i2, op);
+    return JobFwdPlain{ { src, dst, c->primes, c->tw, limbs, c->log_n, mode } };
 }
 
-// ckks_multiply tile loop (evaluator.cpp:714-773) / ckks_square (:1000-1059), fused.
-__device__ __forceinline__ void tensor_at(const u64 *a, const u64 *b, u64 *out, const PrimeDev *primes, int limbs,
-                                          int log_n, size_t i2, int square, int fp)
+static JobInvPlain inv_plain(mhe_ctx *c, const u64 *src, u64 *dst, int limbs, int mode)
 {
-    const size_t i = i2 * 2;
-    const size_t ps = (size_t)limbs << log_n;
-    const int l = (int)(i >> log_n);
-    const PrimeDev p = primes[l];
-    ulonglong2 x0 = *(const ulonglong2 *)(a + i), x1 = *(const ulonglong2 *)(a + ps + i);
-    ulonglong2 r0, r1, r2;
-    if (elem_fp(fp, p))
-    {
-        // FP64: each product in (-1.25q, 1.25q), the cross term's two in (-2.5q, 2.5q), exact
-        const ulonglong2 y0 = square ? x0 : *(const ulonglong2 *)(b + i), y1 = square ? x1 : *(const ulonglong2 *)(b + ps + i);
-        const double qd = p.qd, qi = p.qi;
-        r0.x = fp_canon(mulmod_fd(x0.x, y0.x, p), qd, qi);
-        r0.y = fp_canon(mulmod_fd(x0.y, y0.y, p), qd, qi);
-        r1.x = fp_canon(mulmod_fd(x0.x, y1.x, p) + mulmod_fd(x1.x, y0.x, p), qd, qi);
-        r1.y = fp_canon(mulmod_fd(x0.y, y1.y, p) + mulmod_fd(x1.y, y0.y, p), qd, qi);
-        r2.x = fp_canon(mulmod_fd(x1.x, y1.x, p), qd, qi);
-        r2.y = fp_canon(mulmod_fd(x1.y, y1.y, p), qd, qi);
-    }
-    else if (square)
-    {
-        r0.x = mulmod(x0.x, x0.x, p);
-        r0.y = mulmod(x0.y, x0.y, p);
-        u64 t = mulmod(x0.x, x1.x, p), u = mulmod(x0.y, x1.y, p);
-        r1.x = addmod(t, t, p.q);
-        r1.y = addmod(u, u, p.q);
-        r2.x = mulmod(x1.x, x1.x, p);
-        r2.y = mulmod(x1.y, x1.y, p);
-    }
-    else
-    {
-        ulonglong2 y0 = *(const ulonglong2 *)(b + i), y1 = *(const ulonglong2 *)(b + ps + i);
-        r0.x = mulmod(x0.x, y0.x, p);
-        r0.y = mulmod(x0.y, y0.y, p);
-        r1.x = addmod(mulmod(x0.x, y1.x, p), mulmod(x1.x, y0.x, p), p.q);
-        r1.y = addmod(mulmod(x0.y, y1.y, p), mulmod(x1.y, y0.y, p), p.q);
-        r2.x = mulmod(x1.x, y1.x, p);
-        r2.y = mulmod(x1.y, y1.y, p);
-    }
-    *(ulonglong2 *)(out + i) = r0;
-    *(ulonglong2 *)(out + ps + i) = r1;
-    *(ulonglong2 *)(out + 2 * ps + i) = r2;
+    return JobInvPlain{ { src, dst, c->primes, c->itw, limbs, c->log_n, mode } };
 }
 
-__global__ void k_tensor(const u64 *a, const u64 *b, u64 *out, const PrimeDev *primes, int limbs, int log_n,
-                         size_t total2, int square, int fp)
+// The two special accumulator limbs of the key products acc [2][L+1][n]: inverse NTT in place, lazy.
+static JobStrided special_limbs(mhe_ctx *c, u64 *acc, int L)
 {
-    size_t i2 = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i2 < total2) tensor_at(a, b, out, primes, limbs, log_n, i2, square, fp);
+    u64 *p = acc + (size_t)L * c->n;
+    const size_t stride = (size_t)(L + 1) * c->n;
+    return JobStrided{ p, p, stride, stride, c->K - 1, 0, c->primes, c->itw, c->log_n, 0 };
 }
 
-// The same elementwise kernels over up to MHE_MAXB entries of one shape (entry = blockIdx.y): the
-// launches that mhe_launch_run coalesces, e.g. the same-numbered adds of the images of a
-// seal::FiberBatch
-struct ElemPtrs
+// Forward NTT of [polys][limbs] (limb l on prime l).
+static int run_ntt_fwd(mhe_ctx *c, const u64 *src, u64 *dst, int polys, int limbs, int full, hipStream_t st)
 {
-    const u64 *a[MHE_MAXB];
-    const u64 *b[MHE_MAXB];
-    u64 *out[MHE_MAXB];
-};
-
-__global__ void k_elem_b(ElemPtrs P, const PrimeDev *primes, ScalarTab st, int limbs, int log_n, size_t total2,
-                         int kind, int op, int fp)
-{
-    const size_t i2 = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i2 >= total2) return;
-    const int e = blockIdx.y;
-    switch (kind)
-    {
-    case MHE_LK_ADDSUB: addsub_at(P.a[e], P.b[e], P.out[e], primes, limbs, log_n, i2, op); break;
-    case MHE_LK_MULPLAIN: mulplain_at(P.a[e], P.b[e], P.out[e], primes, limbs, log_n, i2, fp); break;
-    case MHE_LK_MULPLAIN_ADD: mulplain_add_at(P.a[e], P.b[e], P.out[e], primes, limbs, log_n, i2, fp); break;
-    case MHE_LK_SCALAR: scalar_at(P.a[e], P.out[e], primes, st, limbs, log_n, i2, op); break;
-    case MHE_LK_TENSOR: tensor_at(P.a[e], P.b[e], P.out[e], primes, limbs, log_n, i2, op, fp); break;
-    }
+    count_op(c, MHE_OPK_NTT, limbs, (unsigned long long)polys);
+    fwd_col(fwd_plain(c, src, dst, limbs, 0), c->log_n, polys * limbs, c->nm, st);
+    fwd_row(fwd_plain(c, dst, dst, limbs, full), c->log_n, polys * limbs, c->nm, st);
+    HIP_LAUNCH_CHECK();
+    return MHE_OK;
 }
 
-__global__ void k_copy16_b(ElemPtrs P, size_t count)
+static int run_ntt_inv(mhe_ctx *c, const u64 *src, u64 *dst, int polys, int limbs, int full, hipStream_t st)
 {
-    const int e = blockIdx.y;
-    uint4 *dst = reinterpret_cast<uint4 *>(P.out[e]);
-    const uint4 *src = reinterpret_cast<const uint4 *>(P.a[e]);
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (size_t)gridDim.x * 256) dst[i] = src[i];
+    count_op(c, MHE_OPK_NTT, limbs, (unsigned long long)polys);
+    inv_row(inv_plain(c, src, dst, limbs, 0), c->log_n, polys * limbs, c->nm, st);
+    inv_col(inv_plain(c, dst, dst, limbs, full), c->log_n, polys * limbs, c->nm, st);
+    HIP_LAUNCH_CHECK();
+    return MHE_OK;
 }
 
 // Key-switching inner product (evaluator.cpp:2410-2463): for output prime I (I == L -> P),
@@ -1333,401 +730,6 @@ __global__ __launch_bounds__(256) void k_ks_mac(const u64 *modup, const u64 *tar
     r1.y = barrett128(a1y.lo, a1y.hi, p);
     *(ulonglong2 *)(acc + (size_t)I * n + i) = r0;
     *(ulonglong2 *)(acc + (size_t)(L + 1 + I) * n + i) = r1;
-}
-
-// GaloisTool::apply_galois_ntt (util/galois.cpp:192-218) with the permutation of
-// generate_table_ntt (util/galois.cpp:18-51) computed on the fly: out[i] = in[tab(i)].
-__global__ void k_galois(const u64 *in, u64 *out, u32 elt, int log_n, size_t total)
-{
-    size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (g >= total) return;
-    const u32 n = 1u << log_n;
-    const u32 i = (u32)(g & (n - 1));
-    const size_t base = g - i;
-    const u32 reversed = __builtin_bitreverse32(n + i) >> (31 - log_n); // rev over log_n+1 bits
-    const u32 idx = (u32)(((u64)elt * reversed) >> 1) & (n - 1);
-    const u32 src = __builtin_bitreverse32(idx) >> (32 - log_n);
-    out[g] = in[base + src];
-}
-
-// The same for up to MHE_MAXB independent (in, out, element) entries, entry = blockIdx.y.
-struct GalPtrs
-{
-    const u64 *in[MHE_MAXB];
-    u64 *out[MHE_MAXB];
-    u32 elt[MHE_MAXB];
-};
-
-__global__ void k_galois_b(GalPtrs P, int log_n, size_t total)
-{
-    size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (g >= total) return;
-    const u64 *in = P.in[blockIdx.y];
-    u64 *out = P.out[blockIdx.y];
-    const u32 elt = P.elt[blockIdx.y];
-    const u32 n = 1u << log_n;
-    const u32 i = (u32)(g & (n - 1));
-    const size_t base = g - i;
-    const u32 reversed = __builtin_bitreverse32(n + i) >> (31 - log_n);
-    const u32 idx = (u32)(((u64)elt * reversed) >> 1) & (n - 1);
-    const u32 src = __builtin_bitreverse32(idx) >> (32 - log_n);
-    out[g] = in[base + src];
-}
-
-// mhe_rotate_sum: the key products of a chunk's entries folded into their groups' accumulators,
-// before the one ModDown forward NTT per limb of each group.  A chunk's entries come sorted by key
-// (they share the key stream of the MAC), so a group's entries are anywhere in it: zof[e] is the
-// chunk's group of entry e.  Every special limb has been through its own inverse NTT ([0, 2P)), so
-// each lift is SEAL's integer (evaluator.cpp:2466-2524) and the sums that follow are sums of
-// canonical residues mod q_i: the special limbs are never added mod P.
-struct RotSumPtrs
-{
-    const u64 *acc[MHE_MAXB];  // entry: key products [2][L+1][n], special limbs in coefficient form
-    const u64 *perm[MHE_MAXB]; // entry: permuted c0 [L][n]
-    u64 *A[MHE_MAXB];          // group: sum of the key products [2][L+1][n] (limbs 0 .. L-1 used)
-    u64 *T[MHE_MAXB];          // group: sum of the lifted special limbs [2][L][n], coefficient form
-    u64 *out[MHE_MAXB];        // group: out[0] += (or =) the permuted c0s
-    int zof[MHE_MAXB];         // entry: its group among the chunk's
-    int B;                     // entries in the chunk
-    int first[MHE_MAXB];       // group: its first chunk (A and T written, not added to)
-    int write0[MHE_MAXB];      // group: out[0] written, not added to (first chunk without accumulate)
-};
-
-// grid (n / 512, 2 * L, groups in the chunk); one lane owns two adjacent words of (group, k, i)
-__global__ __launch_bounds__(256) void k_rotsum_acc(RotSumPtrs P, const PrimeDev *__restrict__ primes, int L, int K,
-                                                    int log_n)
-{
-    const int z = blockIdx.z, k = blockIdx.y / L, i = blockIdx.y - k * L;
-    const size_t x = ((size_t)blockIdx.x * 256 + threadIdx.x) * 2;
-    const size_t n = (size_t)1 << log_n;
-    JobModDownCol::View v; // the ModDown column pass's lift, with its constants
-    v.p = prime_at(primes, i);
-    v.P = prime_at(primes, K - 1);
-    v.half = v.P.q >> 1;
-    v.fix = v.p.q - barrett64(v.half, v.p);
-    v.reduce = v.P.q > v.p.q;
-    const u64 q = v.p.q;
-    const size_t oa = (size_t)(k * (L + 1) + i) * n + x, os = (size_t)(k * (L + 1) + L) * n + x;
-    const size_t ot = (size_t)(k * L + i) * n + x, oc = (size_t)i * n + x;
-    ulonglong2 a{ 0, 0 }, t{ 0, 0 }, c0{ 0, 0 };
-    if (!P.first[z])
-    {
-        a = *(const ulonglong2 *)(P.A[z] + oa);
-        t = *(const ulonglong2 *)(P.T[z] + ot);
-    }
-    if (k == 0 && !P.write0[z]) c0 = *(const ulonglong2 *)(P.out[z] + oc);
-    for (int e = 0; e < P.B; e++)
-    {
-        if (P.zof[e] != z) continue; // uniform over the workgroup
-        const ulonglong2 ae = *(const ulonglong2 *)(P.acc[e] + oa);
-        const ulonglong2 se = *(const ulonglong2 *)(P.acc[e] + os);
-        a.x = addmod(a.x, ae.x, q);
-        a.y = addmod(a.y, ae.y, q);
-        t.x = addmod(t.x, csub(v.lift(se.x), q), q); // lift() is in [0, 2q)
-        t.y = addmod(t.y, csub(v.lift(se.y), q), q);
-        if (k == 0)
-        {
-            const ulonglong2 ce = *(const ulonglong2 *)(P.perm[e] + oc);
-            c0.x = addmod(c0.x, ce.x, q);
-            c0.y = addmod(c0.y, ce.y, q);
-        }
-    }
-    *(ulonglong2 *)(P.A[z] + oa) = a;
-    *(ulonglong2 *)(P.T[z] + ot) = t;
-    if (k == 0) *(ulonglong2 *)(P.out[z] + oc) = c0;
-}
-
-// Bootstrapper::modraise_inplace (ckks_bootstrapping/Bootstrapper.cpp:2894-2948): the single-limb
-// coefficient-form polynomial x (mod q_0, canonical) is lifted centered, v = x - q_0 if
-// x > q_0/2, and reduced mod every prime of the target level.
-__global__ void k_modraise(const u64 *in, u64 *out, const PrimeDev *primes, int limbs, int log_n, size_t total)
-{
-    size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (g >= total) return;
-    const size_t n = (size_t)1 << log_n;
-    const size_t per_poly = (size_t)limbs << log_n;
-    const size_t p = g / per_poly, r = g - p * per_poly;
-    const int j = (int)(r >> log_n);
-    const size_t i = r & (n - 1);
-    const u64 x = in[p * n + i];
-    const u64 q0 = primes[0].q, q = primes[j].q;
-    u64 v = x % q;
-    if (x > (q0 >> 1))
-    {
-        const u64 mq0 = q - q0 % q; // -q_0 mod q (q for j = 0 reduces to 0 below)
-        v += mq0;
-        v -= (v >= q) ? q : 0;
-    }
-    out[g] = v;
-}
-
-// ============================================================== caching device allocator
-// Stream-ordered allocation for the engine's transient buffers (every Ciphertext temporary of the
-// SEAL surface).  The runtime's stream-ordered pool (hipMallocAsync/hipFreeAsync) was observed on
-// this image to hand out memory that was still live: bootstrapping's cached plaintexts and guard
-// regions were overwritten even with kernels serialised, and disappeared with plain hipMalloc.
-// So the engine keeps its own cache: a freed block records an event on the freeing stream and goes
-// to a free list by size; an allocation reuses a block of the same rounded size (waiting on its
-// event when it comes from another stream) or calls hipMalloc.  Memory is returned to the device
-// only when hipMalloc fails (then every cached block is released and the call retried).
-namespace
-{
-struct CachedBlock
-{
-    void *p;
-    size_t size;
-    hipStream_t st;
-    hipEvent_t ev;
-};
-struct DevAlloc
-{
-    std::mutex mu;
-    std::map<void *, size_t> live;
-    std::multimap<size_t, CachedBlock> free_blocks;
-    std::vector<hipEvent_t> ev_pool;
-    size_t cached = 0, in_use = 0;
-    int contexts = 0; // live engine contexts on this device: the cache is returned when the last goes
-};
-DevAlloc &dev_alloc()
-{
-    static DevAlloc a[64];
-    int d = 0;
-    (void)hipGetDevice(&d);
-    return a[d & 63];
-}
-size_t round_size(size_t b)
-{
-    if (b == 0) b = 1;
-    if (b < ((size_t)1 << 20)) return (b + 4095) & ~(size_t)4095;
-    return (b + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
-}
-void release_cached(DevAlloc &a)
-{
-    // caller holds a.mu
-    (void)hipDeviceSynchronize();
-    for (auto &kv : a.free_blocks)
-    {
-        (void)hipFree(kv.second.p);
-        a.ev_pool.push_back(kv.second.ev);
-    }
-    a.free_blocks.clear();
-    a.cached = 0;
-}
-} // namespace
-
-static void release_cached_blocks()
-{
-    DevAlloc &a = dev_alloc();
-    std::lock_guard<std::mutex> g(a.mu);
-    release_cached(a);
-}
-
-// context lifetime on the current device (mhe_ctx_create / mhe_ctx_destroy): when the last context
-// of a device goes, its cached blocks go back to the device, so another process (or a later
-// engine) on the same GPU gets that memory
-extern "C" __attribute__((visibility("hidden"))) void mhe_internal_ctx_count(int delta)
-{
-    DevAlloc &a = dev_alloc();
-    std::lock_guard<std::mutex> g(a.mu);
-    a.contexts += delta;
-    if (a.contexts <= 0)
-    {
-        a.contexts = 0;
-        release_cached(a);
-    }
-}
-
-extern "C" __attribute__((visibility("hidden"))) hipError_t mhe_internal_alloc(void **p, size_t bytes, hipStream_t st)
-{
-    DevAlloc &a = dev_alloc();
-    const size_t sz = round_size(bytes);
-    std::lock_guard<std::mutex> g(a.mu);
-    auto it = a.free_blocks.lower_bound(sz);
-    auto best = a.free_blocks.end();
-    for (auto j = it; j != a.free_blocks.end() && j->first <= sz + sz / 4; ++j)
-        if (best == a.free_blocks.end() || j->second.st == st)
-        {
-            best = j;
-            if (j->second.st == st) break;
-        }
-    if (best != a.free_blocks.end())
-    {
-        CachedBlock b = best->second;
-        a.free_blocks.erase(best);
-        a.cached -= b.size;
-        if (b.st != st)
-        {
-            hipError_t e = hipStreamWaitEvent(st, b.ev, 0);
-            if (e != hipSuccess) return e;
-        }
-        a.ev_pool.push_back(b.ev);
-        a.live[b.p] = b.size;
-        a.in_use += b.size;
-        *p = b.p;
-        return hipSuccess;
-    }
-    hipError_t e = hipMalloc(p, sz);
-    if (e != hipSuccess)
-    {
-        (void)hipGetLastError();
-        release_cached(a);
-        e = hipMalloc(p, sz);
-        if (e != hipSuccess)
-        {
-            g_alloc_failures.fetch_add(1);
-            return e;
-        }
-        g_alloc_retries.fetch_add(1);
-    }
-    a.live[*p] = sz;
-    a.in_use += sz;
-    return hipSuccess;
-}
-
-extern "C" __attribute__((visibility("hidden"))) hipError_t mhe_internal_free(void *p, hipStream_t st)
-{
-    if (!p) return hipSuccess;
-    DevAlloc &a = dev_alloc();
-    std::lock_guard<std::mutex> g(a.mu);
-    auto it = a.live.find(p);
-    if (it == a.live.end()) return hipErrorInvalidValue;
-    const size_t sz = it->second;
-    a.live.erase(it);
-    a.in_use -= sz;
-    hipEvent_t ev = nullptr;
-    if (!a.ev_pool.empty())
-    {
-        ev = a.ev_pool.back();
-        a.ev_pool.pop_back();
-    }
-    else
-    {
-        hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-        if (e != hipSuccess) return e;
-    }
-    hipError_t e = hipEventRecord(ev, st);
-    if (e != hipSuccess) return e;
-    a.free_blocks.emplace(sz, CachedBlock{ p, sz, st, ev });
-    a.cached += sz;
-    return hipSuccess;
-}
-
-// Device-to-device copies run as a kernel on the caller's stream (ordered with the stream's other
-// kernels by construction, at HBM speed) rather than hipMemcpyAsync's copy engines.
-__global__ void k_copy16(uint4 *__restrict__ dst, const uint4 *__restrict__ src, size_t count)
-{
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (size_t)gridDim.x * 256) dst[i] = src[i];
-}
-
-__global__ void k_copy8(u64 *__restrict__ dst, const u64 *__restrict__ src, size_t count)
-{
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (size_t)gridDim.x * 256) dst[i] = src[i];
-}
-
-extern "C" __attribute__((visibility("hidden"))) hipError_t mhe_internal_copy_d2d(void *dst, const void *src,
-                                                                                  size_t bytes, hipStream_t st)
-{
-    if (!bytes || dst == src) return hipSuccess;
-    const uintptr_t a = (uintptr_t)dst | (uintptr_t)src;
-    if ((a & 15) == 0 && (bytes & 15) == 0)
-    {
-        const size_t cnt = bytes / 16;
-        const unsigned grid = (unsigned)std::min<size_t>((cnt + 255) / 256, 4096);
-        hipLaunchKernelGGL(k_copy16, dim3(grid), dim3(256), 0, st, (uint4 *)dst, (const uint4 *)src, cnt);
-        return hipGetLastError();
-    }
-    if ((a & 7) == 0 && (bytes & 7) == 0)
-    {
-        const size_t cnt = bytes / 8;
-        const unsigned grid = (unsigned)std::min<size_t>((cnt + 255) / 256, 4096);
-        hipLaunchKernelGGL(k_copy8, dim3(grid), dim3(256), 0, st, (u64 *)dst, (const u64 *)src, cnt);
-        return hipGetLastError();
-    }
-    return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st);
-}
-
-// ======================================================================= dispatch helpers
-static bool valid_ctx(mhe_ctx *c)
-{
-    return c && c->primes;
-}
-
-static hipStream_t S(void *s)
-{
-    return (hipStream_t)s;
-}
-
-static int check_limbs(mhe_ctx *c, int limbs, int lo)
-{
-    if (!valid_ctx(c)) return fail(MHE_ERR_ARG, "context is not valid");
-    if (limbs < lo || limbs > c->K - 1) return fail(MHE_ERR_ARG, "encrypted is not valid for encryption parameters");
-    return MHE_OK;
-}
-
-// Do the word ranges [a, a + aw) and [b, b + bw) share a word?  The batched entry points run every
-// entry inside the same kernels, so an output that overlaps another entry's operand would be read
-// and written by one launch in an order that depends on the grid (not the order of count calls).
-static bool ranges_overlap(const u64 *a, size_t aw, const u64 *b, size_t bw)
-{
-    return a < b + bw && b < a + aw;
-}
-
-static void count_op(mhe_ctx *c, int kind, int L, unsigned long long k)
-{
-    if (kind >= 0 && kind < MHE_OPK_KINDS && L >= 0 && L < MHE_OPK_LEVELS) c->opc[kind][L].fetch_add(k, std::memory_order_relaxed);
-}
-
-// launch coalescing (mhe_set_launch_hook): the calling thread's hook, off inside mhe_launch_run
-static thread_local mhe_launch_hook tl_hook = nullptr;
-static thread_local void *tl_hook_user = nullptr;
-static thread_local int tl_hook_off = 0;
-
-// true when the launch was handed to the hook (which ran it and set l.rc)
-static bool hooked(mhe_ctx *c, mhe_launch &l)
-{
-    if (!tl_hook || tl_hook_off) return false;
-    l.rc = -1;
-    tl_hook(c, &l, tl_hook_user);
-    return true;
-}
-
-// Forward NTT of [polys][limbs] (limb l on prime l).
-static int run_ntt_fwd(mhe_ctx *c, const u64 *src, u64 *dst, int polys, int limbs, int full, hipStream_t st)
-{
-    count_op(c, MHE_OPK_NTT, limbs, (unsigned long long)polys);
-    JobFwdPlain j;
-    j.src = src;
-    j.dst = dst;
-    j.primes = c->primes;
-    j.tw = c->tw;
-    j.limbs = limbs;
-    j.log_n = c->log_n;
-    j.mode = 0;
-    fwd_col(j, c->log_n, polys * limbs, c->nm, st);
-    j.src = dst;
-    j.mode = full;
-    fwd_row(j, c->log_n, polys * limbs, c->nm, st);
-    HIP_LAUNCH_CHECK();
-    return MHE_OK;
-}
-
-static int run_ntt_inv(mhe_ctx *c, const u64 *src, u64 *dst, int polys, int limbs, int full, hipStream_t st)
-{
-    count_op(c, MHE_OPK_NTT, limbs, (unsigned long long)polys);
-    JobInvPlain j;
-    j.src = src;
-    j.dst = dst;
-    j.primes = c->primes;
-    j.tw = c->itw;
-    j.limbs = limbs;
-    j.log_n = c->log_n;
-    j.mode = 0;
-    inv_row(j, c->log_n, polys * limbs, c->nm, st);
-    j.src = dst;
-    j.mode = full;
-    inv_col(j, c->log_n, polys * limbs, c->nm, st);
-    HIP_LAUNCH_CHECK();
-    return MHE_OK;
 }
 
 // One entry of a (batched) key switch.
@@ -1779,9 +781,7 @@ static void run_moddown(mhe_ctx *c, const KsJob *jobs, int B, int L, Workspace *
     {
         JobB<JobStrided> j;
         j.per = 2;
-        for (int e = 0; e < B; e++)
-            j.j[e] = JobStrided{ A(e) + (size_t)L * n, A(e) + (size_t)L * n, (size_t)(L + 1) * n,
-                                 (size_t)(L + 1) * n, c->K - 1, 0, c->primes, c->itw, log_n, 0 };
+        for (int e = 0; e < B; e++) j.j[e] = special_limbs(c, A(e), L);
         if (!special_inv_done) inv_row(j, log_n, 2 * B, c->nm, st);
         // the special limbs' inverse column pass runs inside the lift column pass (k_icol_lift)
         // (not in the HMult tail: JobMDRCol reads the fully inverse-transformed special limbs)
@@ -2289,19 +1289,7 @@ MHE_EXPORT int mhe_ctx_destroy(mhe_ctx *c)
     if (!c) return MHE_OK;
     (void)hipSetDevice(c->device);
     for (auto &kv : c->masks) (void)hipFree(kv.second);
-    for (auto &kv : c->ws)
-    {
-        if (kv.second.base) (void)hipFree(kv.second.base);
-        if (kv.second.hoist_base) (void)hipFree(kv.second.hoist_base);
-        if (kv.second.rs_base) (void)hipFree(kv.second.rs_base);
-        if (kv.second.flags) (void)hipFree(kv.second.flags);
-        for (auto &v : kv.second.ev)
-            for (auto &e : v)
-            {
-                (void)hipEventDestroy(e.first);
-                (void)hipEventDestroy(e.second);
-            }
-    }
+    for (auto &kv : c->ws) kv.second.release();
     (void)hipFree(c->primes);
     (void)hipFree(c->tw);
     (void)hipFree(c->itw);
@@ -2327,74 +1315,6 @@ MHE_EXPORT int mhe_malloc(mhe_ctx *c, void **dptr, size_t bytes)
     if (hipMalloc(dptr, bytes ? bytes : 1) != hipSuccess) return fail(MHE_ERR_MEMORY, "device allocation failed");
     return MHE_OK;
 }
-
-// MHE_ALLOC_TRACE=1: track live stream-ordered allocations and report double frees, frees of
-// unknown pointers and overlapping live ranges (debugging aid)
-static std::mutex g_trace_mu;
-static std::map<uintptr_t, size_t> g_live;
-static int trace_on()
-{
-    static int on = -1;
-    if (on < 0)
-    {
-        const char *e = getenv("MHE_ALLOC_TRACE");
-        on = e && e[0] >= '1';
-    }
-    return on;
-}
-
-
-// trace mode: the range [p, p + words) must lie inside one live stream-ordered allocation
-static void trace_range(const char *fn, const char *what, const void *p, size_t words)
-{
-    if (!trace_on() || !p) return;
-    std::lock_guard<std::mutex> g(g_trace_mu);
-    const uintptr_t a = (uintptr_t)p, e = a + words * 8;
-    auto it = g_live.upper_bound(a);
-    if (it == g_live.begin()) return; // not a tracked allocation (workspace, hipMalloc)
-    --it;
-    if (it->first + it->second < a) return;
-    if (e > it->first + it->second)
-        fprintf(stderr, "[alloc-trace] %s: %s range [%p, +%zu words) exceeds allocation %p of %zu words by %zu words\n",
-                fn, what, p, words, (void *)it->first, it->second / 8, (size_t)(e - (it->first + it->second)) / 8);
-}
-// trace level 2: at every instrumented entry, synchronise and check the first 4 KiB of every live
-// allocation's guard; a hit names the previous instrumented call as the writer
-static const char *g_prev_fn = "(none)";
-static size_t g_prev_info[4];
-static void trace_check_all(const char *fn, size_t i0, size_t i1, size_t i2, size_t i3)
-{
-    static int lvl = -1;
-    if (lvl < 0)
-    {
-        const char *e = getenv("MHE_ALLOC_TRACE");
-        lvl = e ? atoi(e) : 0;
-    }
-    if (lvl < 2) return;
-    (void)hipDeviceSynchronize();
-    std::lock_guard<std::mutex> g(g_trace_mu);
-    std::vector<unsigned char> buf(4096);
-    for (auto &kv : g_live)
-    {
-        (void)hipMemcpy(buf.data(), (const char *)kv.first + kv.second, 4096, hipMemcpyDeviceToHost);
-        bool bad = false;
-        for (unsigned char b : buf) bad |= b != 0xAB;
-        if (bad)
-        {
-            fprintf(stderr, "[alloc-trace] guard of %#lx (%zu words) hit before %s; previous call %s(%zu, %zu, %zu, %zu)\n",
-                    (unsigned long)kv.first, kv.second / 8, fn, g_prev_fn, g_prev_info[0], g_prev_info[1],
-                    g_prev_info[2], g_prev_info[3]);
-            (void)hipMemset((char *)kv.first + kv.second, 0xAB, (size_t)16 << 20); // re-arm
-        }
-    }
-    g_prev_fn = fn;
-    g_prev_info[0] = i0;
-    g_prev_info[1] = i1;
-    g_prev_info[2] = i2;
-    g_prev_info[3] = i3;
-}
-#define TR(what, p, words) trace_range(__func__, what, p, (size_t)(words))
-#define TRC(a, b, cc, d) trace_check_all(__func__, (size_t)(a), (size_t)(b), (size_t)(cc), (size_t)(d))
 
 MHE_EXPORT int mhe_malloc_async(mhe_ctx *c, void **dptr, size_t bytes, void *stream)
 {
@@ -2479,43 +1399,14 @@ MHE_EXPORT int mhe_memcpy_d2h(mhe_ctx *c, void *dst, const void *src, size_t byt
 
 MHE_EXPORT int mhe_memcpy_d2d(mhe_ctx *c, void *dst, const void *src, size_t bytes, void *stream)
 {
-    TR("dst", dst, bytes / 8); TR("src", src, bytes / 8);
+    trace_range(__func__, "dst", dst, bytes / 8);
+    trace_range(__func__, "src", src, bytes / 8);
     TRC(0, 0, 0, 0);
     if (!valid_ctx(c)) return fail(MHE_ERR_ARG, "invalid argument");
-    if (bytes && dst != src)
-    {
-        mhe_launch l{};
-        l.kind = MHE_LK_COPY;
-        l.a = (const u64 *)src;
-        l.out = (u64 *)dst;
-        l.bytes = bytes;
-        l.stream = stream;
-        if (hooked(c, l)) return l.rc;
-    }
-    HIP_TRY(mhe_internal_copy_d2d(dst, src, bytes, S(stream)));
-    return MHE_OK;
-}
-
-// one launch as the entry point would have run it (the hook off)
-static int launch_one(mhe_ctx *c, mhe_launch &l)
-{
-    switch (l.kind)
-    {
-    case MHE_LK_ADDSUB:
-        return l.op == 0   ? mhe_add(c, l.a, l.b, l.out, l.polys, l.limbs, l.stream)
-               : l.op == 1 ? mhe_sub(c, l.a, l.b, l.out, l.polys, l.limbs, l.stream)
-                           : mhe_negate(c, l.a, l.out, l.polys, l.limbs, l.stream);
-    case MHE_LK_MULPLAIN: return mhe_multiply_plain(c, l.a, l.b, l.out, l.polys, l.limbs, l.stream);
-    case MHE_LK_MULPLAIN_ADD: return mhe_multiply_plain_add(c, l.a, l.b, l.out, l.polys, l.limbs, l.stream);
-    case MHE_LK_SCALAR:
-        return l.op == 0   ? mhe_multiply_scalar(c, l.a, l.scalars, l.out, l.polys, l.limbs, l.stream)
-               : l.op == 1 ? mhe_add_scalar(c, l.a, l.scalars, l.out, l.polys, l.limbs, l.stream)
-                           : mhe_set_scalar(c, l.scalars, l.out, l.polys, l.limbs, l.stream);
-    case MHE_LK_TENSOR:
-        return l.op ? mhe_ct_square(c, l.a, l.out, l.limbs, l.stream) : mhe_ct_multiply(c, l.a, l.b, l.out, l.limbs, l.stream);
-    case MHE_LK_COPY: return mhe_memcpy_d2d(c, l.out, l.a, l.bytes, l.stream);
-    }
-    return fail(MHE_ERR_ARG, "unknown launch kind");
+    if (!bytes || dst == src) return MHE_OK;
+    mhe_launch l = elem_desc(MHE_LK_COPY, 0, (const u64 *)src, nullptr, (u64 *)dst, 0, 0, stream);
+    l.bytes = bytes;
+    return elem_entry(c, l);
 }
 
 static bool same_shape(const mhe_launch &x, const mhe_launch &y)
@@ -2540,75 +1431,36 @@ MHE_EXPORT int mhe_launch_run(mhe_ctx *c, mhe_launch *const *ls, int count)
 {
     if (!valid_ctx(c)) return fail(MHE_ERR_ARG, "context is not valid");
     if (count < 0 || (count && !ls)) return fail(MHE_ERR_ARG, "invalid argument");
-    struct Off
-    {
-        Off() { tl_hook_off++; }
-        ~Off() { tl_hook_off--; }
-    } off;
+    // every descriptor is checked before the first launch; one that fails keeps its entry point's rc
+    // and takes part in no launch
     std::vector<char> done((size_t)count, 0);
     int first_err = MHE_OK;
+    for (int i = 0; i < count; i++)
+        if ((ls[i]->rc = elem_check(c, *ls[i])))
+        {
+            done[i] = 1;
+            if (!first_err) first_err = ls[i]->rc;
+        }
     for (int i = 0; i < count; i++)
     {
         if (done[i]) continue;
         // entries of i's shape, in order, up to MHE_MAXB per launch
-        int grp[MHE_MAXB], B = 0;
+        mhe_launch *grp[MHE_MAXB];
+        int B = 0;
         for (int j = i; j < count && B < MHE_MAXB; j++)
-            if (!done[j] && same_shape(*ls[i], *ls[j])) grp[B++] = j;
-        for (int k = 0; k < B; k++) done[grp[k]] = 1;
-        mhe_launch &l0 = *ls[grp[0]];
-        const bool aligned16 = l0.kind != MHE_LK_COPY || (l0.bytes & 15) == 0;
-        bool ok_batch = B > 1 && aligned16;
-        if (ok_batch && l0.kind == MHE_LK_COPY)
-            for (int k = 0; k < B; k++)
-                ok_batch = ok_batch && (((uintptr_t)ls[grp[k]]->a | (uintptr_t)ls[grp[k]]->out) & 15) == 0;
-        if (!ok_batch)
-        {
-            for (int k = 0; k < B; k++)
+            if (!done[j] && same_shape(*ls[i], *ls[j]))
             {
-                mhe_launch &l = *ls[grp[k]];
-                l.rc = launch_one(c, l);
-                if (l.rc && !first_err) first_err = l.rc;
+                grp[B++] = ls[j];
+                done[j] = 1;
             }
-            continue;
-        }
-        ElemPtrs P{};
-        for (int k = 0; k < B; k++)
+        // one batched launch, or (a lone descriptor, copies that are not 16-byte aligned) one by one
+        const int step = (B > 1 && elem_batchable(grp, B)) ? B : 1;
+        for (int k = 0; k < B; k += step)
         {
-            P.a[k] = ls[grp[k]]->a;
-            P.b[k] = ls[grp[k]]->b;
-            P.out[k] = ls[grp[k]]->out;
+            const int rc = elem_launch(c, grp + k, step);
+            for (int j = k; j < k + step; j++) grp[j]->rc = rc;
+            if (rc && !first_err) first_err = rc;
         }
-        const hipStream_t st = S(l0.stream);
-        if (l0.kind == MHE_LK_COPY)
-        {
-            const size_t cnt = l0.bytes / 16;
-            const unsigned grid = (unsigned)std::min<size_t>((cnt + 255) / 256, 4096);
-            hipLaunchKernelGGL(k_copy16_b, dim3(grid, (unsigned)B), dim3(256), 0, st, P, cnt);
-        }
-        else
-        {
-            ScalarTab t{};
-            if (l0.kind == MHE_LK_SCALAR)
-                for (int l = 0; l < l0.limbs; l++)
-                {
-                    t.v[l] = l0.scalars[l];
-                    t.vq[l] = host::shoup(l0.scalars[l], c->q[l]);
-                }
-            // a tensor product covers one pair of 2-poly ciphertexts ([limbs] residues per output poly)
-            const size_t total2 = ((size_t)(l0.kind == MHE_LK_TENSOR ? 1 : l0.polys) * l0.limbs << c->log_n) / 2;
-            const int opk = l0.kind == MHE_LK_ADDSUB ? MHE_OPK_ADDSUB
-                            : l0.kind == MHE_LK_SCALAR ? MHE_OPK_SCALAR
-                            : l0.kind == MHE_LK_TENSOR ? MHE_OPK_TENSOR
-                                                        : MHE_OPK_MULPLAIN;
-            count_op(c, opk, l0.limbs, (unsigned long long)B * (l0.kind == MHE_LK_TENSOR ? 1 : l0.polys));
-            if (l0.kind == MHE_LK_MULPLAIN_ADD) count_op(c, MHE_OPK_ADDSUB, l0.limbs, (unsigned long long)B * l0.polys);
-            hipLaunchKernelGGL(k_elem_b, dim3(ELEM_GRID(total2).x, (unsigned)B), dim3(256), 0, st, P, c->primes, t,
-                               l0.limbs, c->log_n, total2, l0.kind, l0.op, c->nm.fp ? 1 : 0);
-        }
-        const hipError_t e = hipGetLastError();
-        const int rc = e == hipSuccess ? MHE_OK : fail(MHE_ERR_DEVICE, hipGetErrorString(e));
-        for (int k = 0; k < B; k++) ls[grp[k]]->rc = rc;
-        if (rc && !first_err) first_err = rc;
     }
     return first_err;
 }
@@ -2686,8 +1538,8 @@ MHE_EXPORT int mhe_scratch_bytes(mhe_ctx *c, uint64_t *workspace, uint64_t *hois
         *workspace = *hoisting = 0;
         for (auto &kv : c->ws)
         {
-            *workspace += kv.second.bytes + kv.second.rs_bytes;
-            *hoisting += kv.second.hoist_bytes;
+            *workspace += kv.second.base.bytes + kv.second.rs_base.bytes;
+            *hoisting += kv.second.hoist_base.bytes;
         }
         *streams = (int)c->ws.size();
     }
@@ -2739,16 +1591,7 @@ MHE_EXPORT int mhe_stream_destroy(mhe_ctx *c, void *stream)
         if (it != c->ws.end())
         {
             (void)hipStreamSynchronize(S(stream));
-            if (it->second.base) (void)hipFree(it->second.base);
-            if (it->second.hoist_base) (void)hipFree(it->second.hoist_base);
-            if (it->second.rs_base) (void)hipFree(it->second.rs_base);
-            if (it->second.flags) (void)hipFree(it->second.flags);
-            for (auto &v : it->second.ev)
-                for (auto &e : v)
-                {
-                    (void)hipEventDestroy(e.first);
-                    (void)hipEventDestroy(e.second);
-                }
+            it->second.release();
             c->ws.erase(it);
         }
     }
@@ -2959,16 +1802,9 @@ MHE_EXPORT int mhe_stream_wait(mhe_ctx *c, void *waiter, void *waitee)
     return MHE_OK;
 }
 
-static int check_poly_args(mhe_ctx *c, const void *a, int polys, int limbs)
-{
-    if (!valid_ctx(c)) return fail(MHE_ERR_ARG, "context is not valid");
-    if (!a || polys < 1 || limbs < 1 || limbs > c->K) return fail(MHE_ERR_ARG, "invalid polynomial arguments");
-    return MHE_OK;
-}
-
 MHE_EXPORT int mhe_ntt_forward(mhe_ctx *c, uint64_t *data, int polys, int limbs, int lazy, void *stream)
 {
-    TR("data", data, (size_t)polys * limbs * ((size_t)1 << c->log_n));
+    TR("data", data, polys, limbs);
     TRC(0, 0, 0, 0);
     int r = check_poly_args(c, data, polys, limbs);
     if (r) return r;
@@ -2977,7 +1813,7 @@ MHE_EXPORT int mhe_ntt_forward(mhe_ctx *c, uint64_t *data, int polys, int limbs,
 
 MHE_EXPORT int mhe_ntt_inverse(mhe_ctx *c, uint64_t *data, int polys, int limbs, int lazy, void *stream)
 {
-    TR("data", data, (size_t)polys * limbs * ((size_t)1 << c->log_n));
+    TR("data", data, polys, limbs);
     TRC(0, 0, 0, 0);
     int r = check_poly_args(c, data, polys, limbs);
     if (r) return r;
@@ -2986,46 +1822,27 @@ MHE_EXPORT int mhe_ntt_inverse(mhe_ctx *c, uint64_t *data, int polys, int limbs,
 
 static int launch_addsub(mhe_ctx *c, const u64 *a, const u64 *b, u64 *out, int polys, int limbs, int op, void *st)
 {
-    int r = check_poly_args(c, a, polys, limbs);
-    if (r) return r;
-    if (!out || (op < 2 && !b)) return fail(MHE_ERR_ARG, "invalid polynomial arguments");
-    {
-        mhe_launch l{};
-        l.kind = MHE_LK_ADDSUB;
-        l.op = op;
-        l.a = a;
-        l.b = b;
-        l.out = out;
-        l.polys = polys;
-        l.limbs = limbs;
-        l.stream = st;
-        if (hooked(c, l)) return l.rc;
-    }
-    count_op(c, MHE_OPK_ADDSUB, limbs, (unsigned long long)polys);
-    size_t total2 = ((size_t)polys * limbs << c->log_n) / 2;
-    hipLaunchKernelGGL(k_addsub, ELEM_GRID(total2), dim3(256), 0, S(st), a, b, out, c->primes, limbs, c->log_n,
-                       total2, op);
-    HIP_LAUNCH_CHECK();
-    return MHE_OK;
+    mhe_launch l = elem_desc(MHE_LK_ADDSUB, op, a, b, out, polys, limbs, st);
+    return elem_entry(c, l);
 }
 
 MHE_EXPORT int mhe_add(mhe_ctx *c, const uint64_t *a, const uint64_t *b, uint64_t *out, int polys, int limbs, void *s)
 {
-    TR("out", out, (size_t)polys * limbs * ((size_t)1 << c->log_n)); TR("a", a, (size_t)polys * limbs * ((size_t)1 << c->log_n)); TR("b", b, (size_t)polys * limbs * ((size_t)1 << c->log_n));
+    TR("out", out, polys, limbs); TR("a", a, polys, limbs); TR("b", b, polys, limbs);
     TRC(0, 0, 0, 0);
     return launch_addsub(c, a, b, out, polys, limbs, 0, s);
 }
 
 MHE_EXPORT int mhe_sub(mhe_ctx *c, const uint64_t *a, const uint64_t *b, uint64_t *out, int polys, int limbs, void *s)
 {
-    TR("out", out, (size_t)polys * limbs * ((size_t)1 << c->log_n)); TR("a", a, (size_t)polys * limbs * ((size_t)1 << c->log_n)); TR("b", b, (size_t)polys * limbs * ((size_t)1 << c->log_n));
+    TR("out", out, polys, limbs); TR("a", a, polys, limbs); TR("b", b, polys, limbs);
     TRC(0, 0, 0, 0);
     return launch_addsub(c, a, b, out, polys, limbs, 1, s);
 }
 
 MHE_EXPORT int mhe_negate(mhe_ctx *c, const uint64_t *a, uint64_t *out, int polys, int limbs, void *s)
 {
-    TR("out", out, (size_t)polys * limbs * ((size_t)1 << c->log_n)); TR("a", a, (size_t)polys * limbs * ((size_t)1 << c->log_n));
+    TR("out", out, polys, limbs); TR("a", a, polys, limbs);
     TRC(0, 0, 0, 0);
     return launch_addsub(c, a, nullptr, out, polys, limbs, 2, s);
 }
@@ -3033,54 +1850,17 @@ MHE_EXPORT int mhe_negate(mhe_ctx *c, const uint64_t *a, uint64_t *out, int poly
 MHE_EXPORT int mhe_multiply_plain(mhe_ctx *c, const uint64_t *a, const uint64_t *b, uint64_t *out, int polys,
                                   int limbs, void *s)
 {
-    TR("out", out, (size_t)polys * limbs * ((size_t)1 << c->log_n)); TR("a", a, (size_t)polys * limbs * ((size_t)1 << c->log_n)); TR("b", b, (size_t)limbs * ((size_t)1 << c->log_n));
+    TR("out", out, polys, limbs); TR("a", a, polys, limbs); TR("b", b, 1, limbs);
     TRC(0, 0, 0, 0);
-    int r = check_poly_args(c, a, polys, limbs);
-    if (r) return r;
-    if (!b || !out) return fail(MHE_ERR_ARG, "invalid polynomial arguments");
-    {
-        mhe_launch l{};
-        l.kind = MHE_LK_MULPLAIN;
-        l.a = a;
-        l.b = b;
-        l.out = out;
-        l.polys = polys;
-        l.limbs = limbs;
-        l.stream = s;
-        if (hooked(c, l)) return l.rc;
-    }
-    count_op(c, MHE_OPK_MULPLAIN, limbs, (unsigned long long)polys);
-    size_t total2 = ((size_t)polys * limbs << c->log_n) / 2;
-    hipLaunchKernelGGL(k_mulplain, ELEM_GRID(total2), dim3(256), 0, S(s), a, b, out, c->primes, limbs, c->log_n,
-                       total2, c->nm.fp ? 1 : 0);
-    HIP_LAUNCH_CHECK();
-    return MHE_OK;
+    mhe_launch l = elem_desc(MHE_LK_MULPLAIN, 0, a, b, out, polys, limbs, s);
+    return elem_entry(c, l);
 }
 
 MHE_EXPORT int mhe_multiply_plain_add(mhe_ctx *c, const uint64_t *a, const uint64_t *b, uint64_t *acc, int polys,
                                       int limbs, void *s)
 {
-    int r = check_poly_args(c, a, polys, limbs);
-    if (r) return r;
-    if (!b || !acc) return fail(MHE_ERR_ARG, "invalid polynomial arguments");
-    {
-        mhe_launch l{};
-        l.kind = MHE_LK_MULPLAIN_ADD;
-        l.a = a;
-        l.b = b;
-        l.out = acc;
-        l.polys = polys;
-        l.limbs = limbs;
-        l.stream = s;
-        if (hooked(c, l)) return l.rc;
-    }
-    count_op(c, MHE_OPK_MULPLAIN, limbs, (unsigned long long)polys);
-    count_op(c, MHE_OPK_ADDSUB, limbs, (unsigned long long)polys);
-    size_t total2 = ((size_t)polys * limbs << c->log_n) / 2;
-    hipLaunchKernelGGL(k_mulplain_add, ELEM_GRID(total2), dim3(256), 0, S(s), a, b, acc, c->primes, limbs, c->log_n,
-                       total2, c->nm.fp ? 1 : 0);
-    HIP_LAUNCH_CHECK();
-    return MHE_OK;
+    mhe_launch l = elem_desc(MHE_LK_MULPLAIN_ADD, 0, a, b, acc, polys, limbs, s);
+    return elem_entry(c, l);
 }
 
 MHE_EXPORT int mhe_multiply_plain_sum(mhe_ctx *c, int count, const uint64_t *const *a, const uint64_t *const *b,
@@ -3112,43 +1892,22 @@ MHE_EXPORT int mhe_multiply_plain_sum(mhe_ctx *c, int count, const uint64_t *con
     return MHE_OK;
 }
 
+// op 2 (set): a is out.  The table is copied into the descriptor once limbs is known to be in range.
 static int launch_scalar(mhe_ctx *c, const u64 *a, const u64 *scalars, u64 *out, int polys, int limbs, int op,
                          void *s)
 {
     int r = check_poly_args(c, a, polys, limbs);
     if (r) return r;
-    if (!scalars || !out) return fail(MHE_ERR_ARG, "invalid polynomial arguments");
-    ScalarTab t;
-    for (int l = 0; l < limbs; l++)
-    {
-        if (scalars[l] >= c->q[l]) return fail(MHE_ERR_ARG, "scalar must be less than modulus");
-        t.v[l] = scalars[l];
-        t.vq[l] = host::shoup(scalars[l], c->q[l]);
-    }
-    {
-        mhe_launch hl{};
-        hl.kind = MHE_LK_SCALAR;
-        hl.op = op;
-        hl.a = a;
-        hl.out = out;
-        hl.polys = polys;
-        hl.limbs = limbs;
-        hl.stream = s;
-        for (int l = 0; l < limbs; l++) hl.scalars[l] = scalars[l];
-        if (hooked(c, hl)) return hl.rc;
-    }
-    count_op(c, MHE_OPK_SCALAR, limbs, (unsigned long long)polys);
-    size_t total2 = ((size_t)polys * limbs << c->log_n) / 2;
-    hipLaunchKernelGGL(k_scalar, ELEM_GRID(total2), dim3(256), 0, S(s), a, out, c->primes, t, limbs, c->log_n,
-                       total2, op);
-    HIP_LAUNCH_CHECK();
-    return MHE_OK;
+    if (!scalars) return fail(MHE_ERR_ARG, "invalid polynomial arguments");
+    mhe_launch l = elem_desc(MHE_LK_SCALAR, op, a, nullptr, out, polys, limbs, s);
+    std::copy(scalars, scalars + limbs, l.scalars);
+    return elem_entry(c, l);
 }
 
 MHE_EXPORT int mhe_multiply_scalar(mhe_ctx *c, const uint64_t *a, const uint64_t *scalars, uint64_t *out, int polys,
                                    int limbs, void *s)
 {
-    TR("out", out, (size_t)polys * limbs * ((size_t)1 << c->log_n)); TR("a", a, (size_t)polys * limbs * ((size_t)1 << c->log_n));
+    TR("out", out, polys, limbs); TR("a", a, polys, limbs);
     TRC(0, 0, 0, 0);
     return launch_scalar(c, a, scalars, out, polys, limbs, 0, s);
 }
@@ -3156,7 +1915,7 @@ MHE_EXPORT int mhe_multiply_scalar(mhe_ctx *c, const uint64_t *a, const uint64_t
 MHE_EXPORT int mhe_add_scalar(mhe_ctx *c, const uint64_t *a, const uint64_t *scalars, uint64_t *out, int polys,
                               int limbs, void *s)
 {
-    TR("out", out, (size_t)polys * limbs * ((size_t)1 << c->log_n)); TR("a", a, (size_t)polys * limbs * ((size_t)1 << c->log_n));
+    TR("out", out, polys, limbs); TR("a", a, polys, limbs);
     TRC(0, 0, 0, 0);
     return launch_scalar(c, a, scalars, out, polys, limbs, 1, s);
 }
@@ -3166,59 +1925,33 @@ MHE_EXPORT int mhe_set_scalar(mhe_ctx *c, const uint64_t *scalars, uint64_t *out
     return launch_scalar(c, out, scalars, out, polys, limbs, 2, s);
 }
 
+// the tensor product inside HMult: operands from the pipeline, not offered to the hook
 static int launch_tensor(mhe_ctx *c, const u64 *a, const u64 *b, u64 *out3, int L, int square, hipStream_t st)
 {
-    count_op(c, MHE_OPK_TENSOR, L, 1);
-    size_t total2 = ((size_t)L << c->log_n) / 2;
-    hipLaunchKernelGGL(k_tensor, ELEM_GRID(total2), dim3(256), 0, st, a, b, out3, c->primes, L, c->log_n, total2,
-                       square, c->nm.fp ? 1 : 0);
-    HIP_LAUNCH_CHECK();
-    return MHE_OK;
+    mhe_launch l = elem_desc(MHE_LK_TENSOR, square, a, b, out3, 2, L, st), *g = &l;
+    return elem_launch(c, &g, 1);
 }
 
 MHE_EXPORT int mhe_ct_multiply(mhe_ctx *c, const uint64_t *a, const uint64_t *b, uint64_t *out3, int limbs, void *s)
 {
-    TR("out3", out3, (size_t)3 * limbs * ((size_t)1 << c->log_n)); TR("a", a, (size_t)2 * limbs * ((size_t)1 << c->log_n)); TR("b", b, (size_t)2 * limbs * ((size_t)1 << c->log_n));
+    TR("out3", out3, 3, limbs); TR("a", a, 2, limbs); TR("b", b, 2, limbs);
     TRC(0, 0, 0, 0);
-    int r = check_poly_args(c, a, 2, limbs);
-    if (r) return r;
-    if (!b || !out3) return fail(MHE_ERR_ARG, "invalid polynomial arguments");
-    mhe_launch l{};
-    l.kind = MHE_LK_TENSOR;
-    l.a = a;
-    l.b = b;
-    l.out = out3;
-    l.polys = 2;
-    l.limbs = limbs;
-    l.stream = s;
-    if (hooked(c, l)) return l.rc;
-    return launch_tensor(c, a, b, out3, limbs, 0, S(s));
+    mhe_launch l = elem_desc(MHE_LK_TENSOR, 0, a, b, out3, 2, limbs, s);
+    return elem_entry(c, l);
 }
 
 MHE_EXPORT int mhe_ct_square(mhe_ctx *c, const uint64_t *a, uint64_t *out3, int limbs, void *s)
 {
-    TR("out3", out3, (size_t)3 * limbs * ((size_t)1 << c->log_n)); TR("a", a, (size_t)2 * limbs * ((size_t)1 << c->log_n));
+    TR("out3", out3, 3, limbs); TR("a", a, 2, limbs);
     TRC(0, 0, 0, 0);
-    int r = check_poly_args(c, a, 2, limbs);
-    if (r) return r;
-    if (!out3) return fail(MHE_ERR_ARG, "invalid polynomial arguments");
-    mhe_launch l{};
-    l.kind = MHE_LK_TENSOR;
-    l.op = 1;
-    l.a = a;
-    l.b = a;
-    l.out = out3;
-    l.polys = 2;
-    l.limbs = limbs;
-    l.stream = s;
-    if (hooked(c, l)) return l.rc;
-    return launch_tensor(c, a, a, out3, limbs, 1, S(s));
+    mhe_launch l = elem_desc(MHE_LK_TENSOR, 1, a, a, out3, 2, limbs, s);
+    return elem_entry(c, l);
 }
 
 MHE_EXPORT int mhe_switch_key(mhe_ctx *c, uint64_t *ct, const uint64_t *target, const uint64_t *key, int key_limbs,
                               int limbs, void *s)
 {
-    TR("ct", ct, (size_t)2 * limbs * ((size_t)1 << c->log_n)); TR("target", target, (size_t)limbs * ((size_t)1 << c->log_n)); TR("key", key, (size_t)limbs * 2 * key_limbs * ((size_t)1 << c->log_n));
+    TR("ct", ct, 2, limbs); TR("target", target, 1, limbs); TR("key", key, 2 * limbs, key_limbs);
     TRC(0, 0, 0, 0);
     int r = check_limbs(c, limbs, 1);
     if (r) return r;
@@ -3228,7 +1961,7 @@ MHE_EXPORT int mhe_switch_key(mhe_ctx *c, uint64_t *ct, const uint64_t *target, 
 
 MHE_EXPORT int mhe_relinearize(mhe_ctx *c, uint64_t *ct3, const uint64_t *key, int key_limbs, int limbs, void *s)
 {
-    TR("ct3", ct3, (size_t)3 * limbs * ((size_t)1 << c->log_n)); TR("key", key, (size_t)limbs * 2 * key_limbs * ((size_t)1 << c->log_n));
+    TR("ct3", ct3, 3, limbs); TR("key", key, 2 * limbs, key_limbs);
     TRC(0, 0, 0, 0);
     int r = check_limbs(c, limbs, 1);
     if (r) return r;
@@ -3250,7 +1983,7 @@ static int launch_galois(mhe_ctx *c, const u64 *in, u32 elt, u64 *out, int polys
 MHE_EXPORT int mhe_permute_galois(mhe_ctx *c, const uint64_t *in, uint32_t elt, uint64_t *out, int polys, int limbs,
                                   void *s)
 {
-    TR("out", out, (size_t)polys * limbs * ((size_t)1 << c->log_n)); TR("in", in, (size_t)polys * limbs * ((size_t)1 << c->log_n));
+    TR("out", out, polys, limbs); TR("in", in, polys, limbs);
     TRC(0, 0, 0, 0);
     int r = check_poly_args(c, in, polys, limbs);
     if (r) return r;
@@ -3261,7 +1994,7 @@ MHE_EXPORT int mhe_permute_galois(mhe_ctx *c, const uint64_t *in, uint32_t elt, 
 MHE_EXPORT int mhe_apply_galois(mhe_ctx *c, uint64_t *ct, uint32_t elt, const uint64_t *key, int key_limbs, int limbs,
                                 void *s)
 {
-    TR("ct", ct, (size_t)2 * limbs * ((size_t)1 << c->log_n)); TR("key", key, (size_t)limbs * 2 * key_limbs * ((size_t)1 << c->log_n));
+    TR("ct", ct, 2, limbs); TR("key", key, 2 * limbs, key_limbs);
     TRC(0, 0, 0, 0);
     int r = check_limbs(c, limbs, 1);
     if (r) return r;
@@ -3284,7 +2017,7 @@ MHE_EXPORT int mhe_apply_galois(mhe_ctx *c, uint64_t *ct, uint32_t elt, const ui
 MHE_EXPORT int mhe_apply_galois_to(mhe_ctx *c, const uint64_t *in, uint64_t *out, uint32_t elt, const uint64_t *key,
                                    int key_limbs, int limbs, void *s)
 {
-    TR("out", out, (size_t)2 * limbs * ((size_t)1 << c->log_n)); TR("in", in, (size_t)2 * limbs * ((size_t)1 << c->log_n));
+    TR("out", out, 2, limbs); TR("in", in, 2, limbs);
     TRC(0, 0, 0, 0);
     int r = check_limbs(c, limbs, 1);
     if (r) return r;
@@ -3325,29 +2058,15 @@ static int get_hoist(mhe_ctx *c, hipStream_t st, int entries, int ws_entries, in
     if (w->hoist_entries < entries || w->hoist_limbs < L)
     {
         const int E = std::max(entries, w->hoist_entries), HL = std::max(L, w->hoist_limbs);
-        HIP_TRY(hipSetDevice(c->device));
-        if (w->hoist_base)
-        {
-            HIP_TRY(hipStreamSynchronize(st));
-            HIP_TRY(hipFree(w->hoist_base));
-        }
-        w->hoist_base = nullptr;
         w->hoist_entries = 0;
         w->hoist_limbs = 0;
-        w->hoist_bytes = 0;
         const size_t per = (size_t)(HL + 1) * HL * c->n, pacc = (size_t)2 * (HL + 1) * c->n;
         const int na = MHE_MAXB * MHE_HOIST_R;
-        const size_t bytes = ((size_t)E * per + (size_t)na * pacc) * sizeof(u64);
-        if (injected_alloc_failure(c) || scratch_alloc((void **)&w->hoist_base, bytes) != hipSuccess)
-        {
-            w->hoist_base = nullptr;
-            return fail(MHE_ERR_MEMORY, "workspace allocation failed");
-        }
-        for (int i = 0; i < E; i++) w->hoist[i] = w->hoist_base + (size_t)i * per;
-        for (int i = 0; i < na; i++) w->hacc[i] = w->hoist_base + (size_t)E * per + (size_t)i * pacc;
+        if ((r = w->hoist_base.grow(c, st, ((size_t)E * per + (size_t)na * pacc) * sizeof(u64)))) return r;
+        for (int i = 0; i < E; i++) w->hoist[i] = w->hoist_base.p + (size_t)i * per;
+        for (int i = 0; i < na; i++) w->hacc[i] = w->hoist_base.p + (size_t)E * per + (size_t)i * pacc;
         w->hoist_entries = E;
         w->hoist_limbs = HL;
-        w->hoist_bytes = bytes;
     }
     if (!w->flags && hipMalloc(&w->flags, MHE_MAXB * sizeof(int)) != hipSuccess)
         return fail(MHE_ERR_MEMORY, "workspace allocation failed");
@@ -3372,17 +2091,8 @@ static int get_mask(mhe_ctx *c, u32 elt, hipStream_t st, const u64 **out)
     HIP_TRY(hipSetDevice(c->device));
     if (hipMalloc(&m, total * sizeof(u64)) != hipSuccess) return fail(MHE_ERR_MEMORY, "Galois mask allocation failed");
     hipLaunchKernelGGL(k_negmask, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, m, elt, c->K, c->log_n);
-    JobFwdPlain j;
-    j.src = m;
-    j.dst = m;
-    j.primes = c->primes;
-    j.tw = c->tw;
-    j.limbs = c->K;
-    j.log_n = c->log_n;
-    j.mode = 0;
-    fwd_col(j, c->log_n, c->K, c->nm, st);
-    j.mode = 1;
-    fwd_row(j, c->log_n, c->K, c->nm, st);
+    fwd_col(fwd_plain(c, m, m, c->K, 0), c->log_n, c->K, c->nm, st);
+    fwd_row(fwd_plain(c, m, m, c->K, 1), c->log_n, c->K, c->nm, st);
     HIP_LAUNCH_CHECK();
     HIP_TRY(hipStreamSynchronize(st));
     c->masks[elt] = m;
@@ -3848,6 +2558,69 @@ MHE_EXPORT int mhe_apply_galois_batch(mhe_ctx *c, int count, const uint64_t *con
 }
 
 // ------------------------------------------------------------------------------ rotate and sum
+// mhe_rotate_sum: the key products of a chunk's entries folded into their groups' accumulators,
+// before the one ModDown forward NTT per limb of each group.  A chunk's entries come sorted by key
+// (they share the key stream of the MAC), so a group's entries are anywhere in it: zof[e] is the
+// chunk's group of entry e.  Every special limb has been through its own inverse NTT ([0, 2P)), so
+// each lift is SEAL's integer (evaluator.cpp:2466-2524) and the sums that follow are sums of
+// canonical residues mod q_i: the special limbs are never added mod P.
+struct RotSumPtrs
+{
+    const u64 *acc[MHE_MAXB];  // entry: key products [2][L+1][n], special limbs in coefficient form
+    const u64 *perm[MHE_MAXB]; // entry: permuted c0 [L][n]
+    u64 *A[MHE_MAXB];          // group: sum of the key products [2][L+1][n] (limbs 0 .. L-1 used)
+    u64 *T[MHE_MAXB];          // group: sum of the lifted special limbs [2][L][n], coefficient form
+    u64 *out[MHE_MAXB];        // group: out[0] += (or =) the permuted c0s
+    int zof[MHE_MAXB];         // entry: its group among the chunk's
+    int B;                     // entries in the chunk
+    int first[MHE_MAXB];       // group: its first chunk (A and T written, not added to)
+    int write0[MHE_MAXB];      // group: out[0] written, not added to (first chunk without accumulate)
+};
+
+// grid (n / 512, 2 * L, groups in the chunk); one lane owns two adjacent words of (group, k, i)
+__global__ __launch_bounds__(256) void k_rotsum_acc(RotSumPtrs P, const PrimeDev *__restrict__ primes, int L, int K,
+                                                    int log_n)
+{
+    const int z = blockIdx.z, k = blockIdx.y / L, i = blockIdx.y - k * L;
+    const size_t x = ((size_t)blockIdx.x * 256 + threadIdx.x) * 2;
+    const size_t n = (size_t)1 << log_n;
+    JobModDownCol::View v; // the ModDown column pass's lift, with its constants
+    v.p = prime_at(primes, i);
+    v.P = prime_at(primes, K - 1);
+    v.half = v.P.q >> 1;
+    v.fix = v.p.q - barrett64(v.half, v.p);
+    v.reduce = v.P.q > v.p.q;
+    const u64 q = v.p.q;
+    const size_t oa = (size_t)(k * (L + 1) + i) * n + x, os = (size_t)(k * (L + 1) + L) * n + x;
+    const size_t ot = (size_t)(k * L + i) * n + x, oc = (size_t)i * n + x;
+    ulonglong2 a{ 0, 0 }, t{ 0, 0 }, c0{ 0, 0 };
+    if (!P.first[z])
+    {
+        a = *(const ulonglong2 *)(P.A[z] + oa);
+        t = *(const ulonglong2 *)(P.T[z] + ot);
+    }
+    if (k == 0 && !P.write0[z]) c0 = *(const ulonglong2 *)(P.out[z] + oc);
+    for (int e = 0; e < P.B; e++)
+    {
+        if (P.zof[e] != z) continue; // uniform over the workgroup
+        const ulonglong2 ae = *(const ulonglong2 *)(P.acc[e] + oa);
+        const ulonglong2 se = *(const ulonglong2 *)(P.acc[e] + os);
+        a.x = addmod(a.x, ae.x, q);
+        a.y = addmod(a.y, ae.y, q);
+        t.x = addmod(t.x, csub(v.lift(se.x), q), q); // lift() is in [0, 2q)
+        t.y = addmod(t.y, csub(v.lift(se.y), q), q);
+        if (k == 0)
+        {
+            const ulonglong2 ce = *(const ulonglong2 *)(P.perm[e] + oc);
+            c0.x = addmod(c0.x, ce.x, q);
+            c0.y = addmod(c0.y, ce.y, q);
+        }
+    }
+    *(ulonglong2 *)(P.A[z] + oa) = a;
+    *(ulonglong2 *)(P.T[z] + ot) = t;
+    if (k == 0) *(ulonglong2 *)(P.out[z] + oc) = c0;
+}
+
 // The scratch of mhe_rotate_sum on stream st: the workspace for `entries` batch entries and the
 // accumulators of MHE_MAXB groups at L limbs (grown, after draining the stream, when a call needs a
 // higher level).
@@ -3859,23 +2632,9 @@ static int get_rotsum(mhe_ctx *c, hipStream_t st, int entries, int L, Workspace 
     std::lock_guard<std::mutex> g(w->mu);
     if (w->rs_limbs < L)
     {
-        HIP_TRY(hipSetDevice(c->device));
-        if (w->rs_base)
-        {
-            HIP_TRY(hipStreamSynchronize(st));
-            HIP_TRY(hipFree(w->rs_base));
-        }
-        w->rs_base = nullptr;
         w->rs_limbs = 0;
-        w->rs_bytes = 0;
-        const size_t bytes = (size_t)MHE_MAXB * (4 * (size_t)L + 2) * c->n * sizeof(u64);
-        if (injected_alloc_failure(c) || scratch_alloc((void **)&w->rs_base, bytes) != hipSuccess)
-        {
-            w->rs_base = nullptr;
-            return fail(MHE_ERR_MEMORY, "workspace allocation failed");
-        }
+        if ((r = w->rs_base.grow(c, st, (size_t)MHE_MAXB * (4 * (size_t)L + 2) * c->n * sizeof(u64)))) return r;
         w->rs_limbs = L;
-        w->rs_bytes = bytes;
     }
     *out = w;
     return MHE_OK;
@@ -3949,7 +2708,7 @@ MHE_EXPORT int mhe_rotate_sum(mhe_ctx *c, int count, const uint64_t *const *in, 
     Workspace *w;
     if ((r = get_rotsum(c, st, std::min(count, MHE_MAXB), L, &w))) return r;
     const size_t rs_per = (4 * (size_t)w->rs_limbs + 2) * n;
-    auto A_of = [&](int slot) { return w->rs_base + (size_t)slot * rs_per; };
+    auto A_of = [&](int slot) { return w->rs_base.p + (size_t)slot * rs_per; };
     auto T_of = [&](int slot) { return A_of(slot) + 2 * (size_t)(L + 1) * n; };
     // rounds of at most MHE_MAXB groups: their entries, those of one key side by side (a launch of
     // them shares the key stream, k_ks_row_mac share), in chunks of at most MHE_MAXB that cut across
@@ -4008,9 +2767,7 @@ MHE_EXPORT int mhe_rotate_sum(mhe_ctx *c, int count, const uint64_t *const *in, 
             // each entry's special limbs through their own inverse NTT, [0, 2P)
             JobB<JobStrided> sj;
             sj.per = 2;
-            for (int e = 0; e < B; e++)
-                sj.j[e] = JobStrided{ w->e[e].acc + (size_t)L * n, w->e[e].acc + (size_t)L * n, (size_t)(L + 1) * n,
-                                      (size_t)(L + 1) * n, c->K - 1, 0, c->primes, c->itw, c->log_n, 0 };
+            for (int e = 0; e < B; e++) sj.j[e] = special_limbs(c, w->e[e].acc, L);
             if (!special_inv_done) inv_row(sj, c->log_n, 2 * B, c->nm, st);
             inv_col(sj, c->log_n, 2 * B, c->nm, st);
             hipLaunchKernelGGL(k_rotsum_acc, dim3((unsigned)(n / 512), (unsigned)(2 * L), (unsigned)Z), dim3(256), 0, st,
@@ -4025,15 +2782,7 @@ MHE_EXPORT int mhe_rotate_sum(mhe_ctx *c, int count, const uint64_t *const *in, 
         dr.per = 2 * L;
         for (int z = 0; z < G; z++)
         {
-            JobFwdPlain f;
-            f.src = T_of(z);
-            f.dst = T_of(z);
-            f.primes = c->primes;
-            f.tw = c->tw;
-            f.limbs = L;
-            f.log_n = c->log_n;
-            f.mode = 0;
-            fc.j[z] = f;
+            fc.j[z] = fwd_plain(c, T_of(z), T_of(z), L, 0);
             dr.j[z] = JobModDownRow{ T_of(z), A_of(z), out[g0 + z], c->primes, c->tw, c->invq, L, c->K, c->log_n };
             dr.j[z].fp = c->nm.fp ? 1 : 0;
             dr.j[z].c1_write = accumulate ? 0 : 1;
@@ -4105,7 +2854,7 @@ MHE_EXPORT int mhe_switch_key_batch(mhe_ctx *c, int count, uint64_t *const *ct, 
 
 MHE_EXPORT int mhe_rescale_to_next(mhe_ctx *c, const uint64_t *in, uint64_t *out, int size, int limbs, void *s)
 {
-    TR("out", out, (size_t)size * (limbs - 1) * ((size_t)1 << c->log_n)); TR("in", in, (size_t)size * limbs * ((size_t)1 << c->log_n));
+    TR("out", out, size, (limbs - 1)); TR("in", in, size, limbs);
     TRC(0, 0, 0, 0);
     if (!valid_ctx(c)) return fail(MHE_ERR_ARG, "context is not valid");
     if (limbs < 2) return fail(MHE_ERR_RANGE, "end of modulus switching chain reached");
@@ -4117,7 +2866,7 @@ MHE_EXPORT int mhe_rescale_to_next(mhe_ctx *c, const uint64_t *in, uint64_t *out
 
 MHE_EXPORT int mhe_modraise(mhe_ctx *c, const uint64_t *in, uint64_t *out, int size, int limbs, void *s)
 {
-    TR("out", out, (size_t)size * limbs * ((size_t)1 << c->log_n)); TR("in", in, (size_t)size * ((size_t)1 << c->log_n));
+    TR("out", out, size, limbs); TR("in", in, size, 1);
     TRC(0, 0, 0, 0);
     if (!valid_ctx(c)) return fail(MHE_ERR_ARG, "context is not valid");
     if (!in || !out || size < 1 || limbs < 1 || limbs > c->K) return fail(MHE_ERR_ARG, "invalid polynomial arguments");
@@ -4130,7 +2879,7 @@ MHE_EXPORT int mhe_modraise(mhe_ctx *c, const uint64_t *in, uint64_t *out, int s
 
 MHE_EXPORT int mhe_mod_switch_drop(mhe_ctx *c, const uint64_t *in, uint64_t *out, int size, int limbs, void *s)
 {
-    TR("out", out, (size_t)size * (limbs - 1) * ((size_t)1 << c->log_n)); TR("in", in, (size_t)size * limbs * ((size_t)1 << c->log_n));
+    TR("out", out, size, (limbs - 1)); TR("in", in, size, limbs);
     TRC(0, 0, 0, 0);
     if (!valid_ctx(c)) return fail(MHE_ERR_ARG, "context is not valid");
     if (limbs < 2) return fail(MHE_ERR_RANGE, "end of modulus switching chain reached");

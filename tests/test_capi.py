@@ -52,6 +52,48 @@ def test_galois_elt_from_step():
     assert mhe.galois_elt_from_step(16, 1 << 15) == 0  # step count too large
 
 
+NULL_CTX_ENTRY_POINTS = [
+    "mhe_ntt_forward", "mhe_ntt_inverse", "mhe_add", "mhe_sub", "mhe_negate", "mhe_multiply_plain",
+    "mhe_multiply_scalar", "mhe_add_scalar", "mhe_ct_multiply", "mhe_ct_square", "mhe_switch_key",
+    "mhe_relinearize", "mhe_permute_galois", "mhe_apply_galois", "mhe_apply_galois_to", "mhe_rescale_to_next",
+    "mhe_modraise", "mhe_mod_switch_drop"]
+
+_NULL_CTX_CHILD = """
+import ctypes, json, sys
+lib = ctypes.CDLL(sys.argv[1])
+kinds = {"p": ctypes.c_void_p, "i": ctypes.c_int, "u": ctypes.c_uint32}
+for name, sig in json.loads(sys.argv[2]):
+    f = getattr(lib, name)
+    f.restype = ctypes.c_int
+    f.argtypes = [kinds[k] for k in sig]
+    rc = f(*[kinds[k](0) for k in sig])
+    print(name, rc, flush=True)
+"""
+
+
+def test_null_context_is_an_argument_error():
+    """Every entry point that traces its operands returns MHE_ERR_ARG for a null context (all other
+    arguments zero / null) instead of reading through it.  A fresh child process that only loads the
+    library: it never creates a context, so it opens no GPU, and a crash cannot take the suite down."""
+    import subprocess
+    import sys
+
+    def code(t):
+        return "i" if t is ctypes.c_int else "u" if t is ctypes.c_uint32 else "p"
+
+    assert len(NULL_CTX_ENTRY_POINTS) == 18
+    sigs = []
+    for name in NULL_CTX_ENTRY_POINTS:
+        res, args = mhe.SIGNATURES[name]
+        assert res is ctypes.c_int
+        sigs.append((name, "".join(code(t) for t in args)))
+    p = subprocess.run([sys.executable, "-c", _NULL_CTX_CHILD, mhe.LIB_PATH, json.dumps(sigs)],
+                       capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, (p.returncode, p.stdout, p.stderr)
+    got = [line.split() for line in p.stdout.splitlines()]
+    assert got == [[name, "-1"] for name in NULL_CTX_ENTRY_POINTS], (got, p.stderr)
+
+
 def test_ctx_create_rejects_bad_chain_without_gpu_work():
     lib = mhe.lib()
     h = ctypes.c_void_p()

@@ -13,6 +13,7 @@ from test_gpu_parity import SMALL_BITS, Chain, _variant_chain
 pytestmark = pytest.mark.gpu
 
 COUNTS = [1, 3, 8, 11]  # one by one; merged; one full merged launch; 8 + 3
+MHE_ERR_ARG = -1        # include/mhe.h
 
 
 @pytest.fixture(scope="module")
@@ -215,6 +216,26 @@ def test_launch_run_mixed_shapes(small):
     assert ch.eng.launch_run([c.d for c in cases]) == 0
     for i, c in enumerate(cases):
         c.check(i)
+
+
+# ------------------------------------------------------------------------- invalid descriptor
+def test_launch_run_rejects_out_of_range_scalar_table(small):
+    """Three scalar multiplies that would merge share a table whose first scalar is q_0: each gets the
+    rc of mhe_multiply_scalar (MHE_ERR_ARG) and takes part in no launch, so its output keeps the
+    sentinel; the valid add of the same call runs."""
+    ch = small
+    L = ch.K - 1
+    s = rand_scalars(ch, L)
+    bad = [Case(ch, "scalar_multiply", L, scalars=s) for _ in range(3)]
+    for c in bad:
+        c.d.scalars[0] = ch.moduli[0]  # the shared table, now out of range in limb 0
+        c.out.fill_(-1)
+    good = Case(ch, "add", L)
+    assert ch.eng.launch_run([bad[0].d, good.d, bad[1].d, bad[2].d]) == MHE_ERR_ARG
+    for c in bad:
+        assert c.d.rc == MHE_ERR_ARG
+        assert (ch.down(c.out) == np.uint64(0xFFFFFFFFFFFFFFFF)).all()
+    good.check()
 
 
 # ------------------------------------------------------------------------------- op counts
