@@ -1001,16 +1001,20 @@ private:
                            Rmode mode, const RelinKeys *relin_keys) const;
     void switch_key(Ciphertext &encrypted, const std::uint64_t *target_dev, const KSwitchKeys &keys,
                     std::size_t index) const;
-    void rotate_internal(Ciphertext &encrypted, int steps, const GaloisKeys &galois_keys) const;
+    void rotate_internal(const Ciphertext &encrypted, int steps, const GaloisKeys &galois_keys,
+                         Ciphertext &destination) const;
     // Lockstep: hand `op` to the calling thread's group (false: no group, run it directly)
     bool lockstep_submit(LsOp &op) const;
+    // a merge point: when the calling thread is merging, the LsOp that make() returns is submitted
+    // (true: the group ran the call)
+    template <class Make>
+    bool merge_point(Make make, bool group_only = false) const;
     friend struct Lockstep::Impl;
     friend class FiberBatch;
     void lockstep_execute(std::vector<LsOp *> &ops) const;
     // rotate_sum of every op (one mhe_rotate_sum, one group per op); false, with nothing written,
     // when an op has to take the one-by-one path
     bool rotate_sum_merged(const std::vector<LsOp *> &ops) const;
-    std::size_t limbs_of(const parms_id_type &id) const;
     SEALContext context_;
     CKKSEncoder &encoder_;
     struct VecCache;

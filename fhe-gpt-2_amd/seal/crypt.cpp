@@ -1,0 +1,325 @@
+// crypt.cpp -- CKKSEncoder (ckks.h/ckks.cpp), Encryptor (encryptor.cpp:88-239) and Decryptor
+// (decryptor.cpp ckks_decrypt).
+#include "seal_internal.h"
+#include "random_internal.h"
+
+#include <complex>
+
+namespace seal
+{
+// ------------------------------------------------------------------------------ CKKSEncoder
+CKKSEncoder::CKKSEncoder(const SEALContext &context) : ctx_(context)
+{
+    require_set(context);
+    const auto &parms = context.first_context_data()->parms();
+    const std::size_t n = parms.poly_modulus_degree();
+    slots_ = n >> 1;
+    sparse_slots_ = parms.sparse_slots() ? parms.sparse_slots() : slots_;
+    chk(mhe_encoder_create(&enc_, __builtin_ctzll(n)));
+}
+
+CKKSEncoder::~CKKSEncoder()
+{
+    if (enc_) (void)mhe_encoder_destroy(enc_);
+}
+
+void CKKSEncoder::encode_internal(const double *re, const double *im, std::size_t count, parms_id_type parms_id,
+                                  double scale, Plaintext &destination)
+{
+    auto cd = ctx_.get_context_data(parms_id);
+    if (!cd) throw std::invalid_argument("parms_id is not valid for encryption parameters");
+    const std::size_t L = cd->parms().coeff_modulus().size();
+    if (count > slots_) throw std::invalid_argument("values_size is too large");
+    void *s = ctx_.stream();
+    destination.set_level(ctx_, parms_id, L);
+    destination.scale() = scale;
+    chk(mhe_ckks_encode(ctx_.engine(), enc_, re, im, count, scale, (int)L, destination.store().dev_write(s, true),
+                        s));
+}
+
+void CKKSEncoder::encode(const std::vector<double> &values, parms_id_type parms_id, double scale,
+                         Plaintext &destination, MemoryPoolHandle)
+{
+    TRACE_OP("encode", trace::pt(destination), trace::vec(values.data(), nullptr, values.size()));
+    TRACE_EXTRA("\"scale\": " + trace::num(scale));
+    encode_internal(values.data(), nullptr, values.size(), parms_id, scale, destination);
+}
+
+void CKKSEncoder::encode(const std::vector<std::complex<double>> &values, parms_id_type parms_id, double scale,
+                         Plaintext &destination, MemoryPoolHandle)
+{
+    std::vector<double> re(values.size()), im(values.size());
+    for (std::size_t i = 0; i < values.size(); i++)
+    {
+        re[i] = values[i].real();
+        im[i] = values[i].imag();
+    }
+    TRACE_OP("encode", trace::pt(destination), trace::vec(re.data(), im.data(), re.size()));
+    TRACE_EXTRA("\"scale\": " + trace::num(scale));
+    encode_internal(re.data(), im.data(), values.size(), parms_id, scale, destination);
+}
+
+void CKKSEncoder::encode(const std::vector<double> &values, double scale, Plaintext &destination, MemoryPoolHandle)
+{
+    encode(values, ctx_.first_parms_id(), scale, destination);
+}
+
+void CKKSEncoder::encode(const std::vector<std::complex<double>> &values, double scale, Plaintext &destination,
+                         MemoryPoolHandle)
+{
+    encode(values, ctx_.first_parms_id(), scale, destination);
+}
+
+void CKKSEncoder::encode(double value, parms_id_type parms_id, double scale, Plaintext &destination, MemoryPoolHandle)
+{
+    TRACE_OP("encode_const", trace::pt(destination));
+    TRACE_EXTRA("\"value\": " + trace::num(value) + ", \"scale\": " + trace::num(scale) + ", \"limbs\": " +
+                std::to_string(ctx_.get_context_data(parms_id) ? ctx_.get_context_data(parms_id)->parms().coeff_modulus().size() : 0));
+    auto cd = ctx_.get_context_data(parms_id);
+    if (!cd) throw std::invalid_argument("parms_id is not valid for encryption parameters");
+    const std::size_t L = cd->parms().coeff_modulus().size();
+    std::vector<std::uint64_t> r(L);
+    chk(mhe_ckks_encode_scalar(ctx_.engine(), value, scale, (int)L, r.data()));
+    void *s = ctx_.stream();
+    destination.set_level(ctx_, parms_id, L);
+    destination.scale() = scale;
+    chk(mhe_set_scalar(ctx_.engine(), r.data(), destination.store().dev_write(s, true), 1, (int)L, s));
+}
+
+void CKKSEncoder::encode(double value, double scale, Plaintext &destination, MemoryPoolHandle)
+{
+    encode(value, ctx_.first_parms_id(), scale, destination);
+}
+
+void CKKSEncoder::decode_internal(const Plaintext &plain, std::vector<std::complex<double>> &out)
+{
+    if (!plain.is_ntt_form()) throw std::invalid_argument("plain is not in NTT form");
+    auto cd = ctx_.get_context_data(plain.parms_id());
+    if (!cd) throw std::invalid_argument("plain is not valid for encryption parameters");
+    const std::size_t L = cd->parms().coeff_modulus().size();
+    std::vector<double> re(sparse_slots_), im(sparse_slots_);
+    void *s = ctx_.stream();
+    chk(mhe_ckks_decode(ctx_.engine(), enc_, plain.store().dev_read(s), (int)L, plain.scale(),
+                        sparse_slots_ == slots_ ? 0 : sparse_slots_, re.data(), im.data(), s));
+    out.resize(sparse_slots_);
+    for (std::size_t i = 0; i < sparse_slots_; i++) out[i] = { re[i], im[i] };
+}
+
+void CKKSEncoder::decode(const Plaintext &plain, std::vector<std::complex<double>> &destination, MemoryPoolHandle)
+{
+    decode_internal(plain, destination);
+}
+
+void CKKSEncoder::decode(const Plaintext &plain, std::vector<double> &destination, MemoryPoolHandle)
+{
+    std::vector<std::complex<double>> z;
+    decode_internal(plain, z);
+    destination.resize(z.size());
+    for (std::size_t i = 0; i < z.size(); i++) destination[i] = z[i].real();
+}
+
+// ------------------------------------------------------------------------------ Encryptor
+Encryptor::Encryptor(const SEALContext &context, const PublicKey &public_key)
+    : ctx_(context), pk_(public_key), asymmetric_(true)
+{
+    require_set(context);
+    if (public_key.parms_id() != context.key_parms_id())
+        throw std::invalid_argument("public key is not valid for encryption parameters");
+    rng_ = factory_of(context);
+}
+
+Encryptor::Encryptor(const SEALContext &context, const SecretKey &secret_key)
+    : ctx_(context), sk_(secret_key), asymmetric_(false), has_sk_(true)
+{
+    require_set(context);
+    if (secret_key.parms_id() != context.key_parms_id())
+        throw std::invalid_argument("secret key is not valid for encryption parameters");
+    rng_ = factory_of(context);
+}
+
+Encryptor::Encryptor(const SEALContext &context, const PublicKey &public_key, const SecretKey &secret_key)
+    : Encryptor(context, public_key)
+{
+    set_secret_key(secret_key);
+}
+
+void Encryptor::set_public_key(const PublicKey &public_key)
+{
+    if (public_key.parms_id() != ctx_.key_parms_id())
+        throw std::invalid_argument("public key is not valid for encryption parameters");
+    pk_ = public_key;
+    asymmetric_ = true;
+}
+
+void Encryptor::set_secret_key(const SecretKey &secret_key)
+{
+    if (secret_key.parms_id() != ctx_.key_parms_id())
+        throw std::invalid_argument("secret key is not valid for encryption parameters");
+    sk_ = secret_key;
+    has_sk_ = true;
+}
+
+void Encryptor::encrypt_zero_at(std::size_t L, Ciphertext &dest, bool symmetric, prng_seed_type *public_seed) const
+{
+    // encryptor.cpp:88-166 (encrypt_zero_internal): public-key encryption runs one level up
+    // (the key level for the first data level) and is divided and rounded down by the dropped
+    // prime; secret-key encryption runs at the level itself.
+    const std::size_t K = ctx_.key_size(), n = ctx_.key_context_data()->parms().poly_modulus_degree();
+    mhe_ctx *eng = ctx_.engine();
+    void *s = ctx_.stream();
+    std::uint64_t *d = dest.store().dev_write(s, true);
+    const prng_seed_type seed = rng_->next_seed();
+    if (symmetric)
+    {
+        if (!has_sk_) throw std::logic_error("secret key is not set");
+        sym_encrypt_zero(ctx_, seed, sk_.data().store().dev_read(s), L, d, d + L * n, s);
+        if (public_seed) *public_seed = rnd::stream_prefix_seed(seed);
+        return;
+    }
+    if (!asymmetric_) throw std::logic_error("public key is not set");
+    // encrypt_zero_asymmetric (rlwe.cpp:220-286): one PRNG; u ternary, then e_0, e_1 (CBD)
+    const std::size_t m = L < K ? L + 1 : L;
+    const std::uint64_t *pk = pk_.data().store().dev_read(s);
+    DevBuf u(eng, s, m * n), c(eng, s, 2 * m * n), e(eng, s, 2 * m * n), state(eng, s, 1);
+    auto *st = reinterpret_cast<std::uint32_t *>(state.p);
+    chk(mhe_prng_small(eng, seed.data(), 0, MHE_SAMPLE_TERNARY, (int)m, u.p, st, s));
+    chk(mhe_prng_small(eng, seed.data(), 4 * n, MHE_SAMPLE_CBD, (int)m, e.p, st, s));
+    chk(mhe_prng_small(eng, seed.data(), 10 * n, MHE_SAMPLE_CBD, (int)m, e.p + m * n, st, s));
+    chk(mhe_ntt_forward(eng, u.p, 1, (int)m, 0, s));
+    chk(mhe_ntt_forward(eng, e.p, 2, (int)m, 0, s));
+    for (int j = 0; j < 2; j++)
+    {
+        // pk_j restricted to the first m primes: limbs 0..m-1 of poly j ([2][K][n] layout)
+        chk(mhe_multiply_plain(eng, u.p, pk + j * K * n, c.p + j * m * n, 1, (int)m, s));
+        chk(mhe_add(eng, e.p + j * m * n, c.p + j * m * n, c.p + j * m * n, 1, (int)m, s));
+    }
+    if (m == L)
+        chk(mhe_memcpy_d2d(eng, d, c.p, 2 * L * n * 8, s));
+    else
+        chk(mhe_rescale_to_next(eng, c.p, d, 2, (int)m, s));
+}
+
+void Encryptor::zero_at(parms_id_type parms_id, Ciphertext &destination, bool symmetric,
+                        prng_seed_type *public_seed) const
+{
+    auto cd = ctx_.get_context_data(parms_id);
+    if (!cd) throw std::invalid_argument("parms_id is not valid for encryption parameters");
+    destination.resize(ctx_, parms_id, 2);
+    destination.is_ntt_form() = true;
+    destination.scale() = 1.0;
+    encrypt_zero_at(cd->parms().coeff_modulus().size(), destination, symmetric, public_seed);
+}
+
+void Encryptor::encrypt_zero(parms_id_type parms_id, Ciphertext &destination, MemoryPoolHandle) const
+{
+    // SEAL's encrypt_zero / encrypt are public-key encryptions (encryptor.h:158-164, encryptor.cpp:
+    // 177-181): without a public key they throw, even when a secret key is set
+    zero_at(parms_id, destination, false, nullptr);
+}
+
+void Encryptor::encrypt_zero(Ciphertext &destination, MemoryPoolHandle pool) const
+{
+    encrypt_zero(ctx_.first_parms_id(), destination, pool);
+}
+
+void Encryptor::encrypt_zero_symmetric(parms_id_type parms_id, Ciphertext &destination, MemoryPoolHandle) const
+{
+    zero_at(parms_id, destination, true, nullptr);
+}
+
+void Encryptor::encrypt_zero_symmetric(Ciphertext &destination, MemoryPoolHandle pool) const
+{
+    encrypt_zero_symmetric(ctx_.first_parms_id(), destination, pool);
+}
+
+Serializable<Ciphertext> Encryptor::encrypt_zero_symmetric(parms_id_type parms_id, MemoryPoolHandle) const
+{
+    Ciphertext c;
+    prng_seed_type seed{};
+    zero_at(parms_id, c, true, &seed);
+    return Serializable<Ciphertext>(std::move(c), SeedMap{ { 0, { seed } } });
+}
+
+Serializable<Ciphertext> Encryptor::encrypt_zero_symmetric(MemoryPoolHandle pool) const
+{
+    return encrypt_zero_symmetric(ctx_.first_parms_id(), pool);
+}
+
+void Encryptor::encrypt(const Plaintext &plain, Ciphertext &destination, MemoryPoolHandle) const
+{
+    encrypt_plain(plain, destination, false, nullptr);
+}
+
+Serializable<Ciphertext> Encryptor::encrypt(const Plaintext &plain, MemoryPoolHandle) const
+{
+    // a public-key encryption has no seed to save (encrypt_symmetric is the seeded form)
+    Ciphertext c;
+    encrypt_plain(plain, c, false, nullptr);
+    return Serializable<Ciphertext>(std::move(c), SeedMap{});
+}
+
+void Encryptor::encrypt_symmetric(const Plaintext &plain, Ciphertext &destination, MemoryPoolHandle) const
+{
+    encrypt_plain(plain, destination, true, nullptr);
+}
+
+Serializable<Ciphertext> Encryptor::encrypt_symmetric(const Plaintext &plain, MemoryPoolHandle) const
+{
+    Ciphertext c;
+    prng_seed_type seed{};
+    encrypt_plain(plain, c, true, &seed);
+    return Serializable<Ciphertext>(std::move(c), SeedMap{ { 0, { seed } } });
+}
+
+void Encryptor::encrypt_plain(const Plaintext &plain, Ciphertext &destination, bool symmetric,
+                              prng_seed_type *public_seed) const
+{
+    TRACE_OP("encrypt", trace::ct(destination), trace::pt(plain));
+    // encrypt_internal (encryptor.cpp:168-239), CKKS branch: the plaintext is added to c0 only, so a
+    // symmetric encryption keeps c1 = the seeded uniform polynomial
+    if (!plain.is_ntt_form()) throw std::invalid_argument("plain must be in NTT form");
+    auto cd = ctx_.get_context_data(plain.parms_id());
+    if (!cd) throw std::invalid_argument("plain is not valid for encryption parameters");
+    const std::size_t L = cd->parms().coeff_modulus().size();
+    zero_at(plain.parms_id(), destination, symmetric, public_seed);
+    void *s = ctx_.stream();
+    std::uint64_t *d = destination.store().dev_write(s);
+    chk(mhe_add(ctx_.engine(), d, plain.store().dev_read(s), d, 1, (int)L, s));
+    destination.scale() = plain.scale();
+}
+
+// ------------------------------------------------------------------------------ Decryptor
+Decryptor::Decryptor(const SEALContext &context, const SecretKey &secret_key) : ctx_(context), sk_(secret_key)
+{
+    require_set(context);
+    if (secret_key.parms_id() != context.key_parms_id())
+        throw std::invalid_argument("secret key is not valid for encryption parameters");
+}
+
+void Decryptor::decrypt(const Ciphertext &encrypted, Plaintext &destination)
+{
+    // decryptor.cpp ckks_decrypt: <(c0, c1, c2, ...), (1, s, s^2, ...)> in NTT form
+    auto cd = ctx_.get_context_data(encrypted.parms_id());
+    if (!cd || encrypted.size() < 2) throw std::invalid_argument("encrypted is not valid for encryption parameters");
+    if (!encrypted.is_ntt_form()) throw std::invalid_argument("encrypted must be in NTT form");
+    const std::size_t L = cd->parms().coeff_modulus().size(), n = cd->parms().poly_modulus_degree();
+    mhe_ctx *eng = ctx_.engine();
+    void *s = ctx_.stream();
+    const std::uint64_t *c = encrypted.store().dev_read(s);
+    const std::uint64_t *sk = sk_.data().store().dev_read(s);
+    Plaintext out;
+    out.set_level(ctx_, encrypted.parms_id(), L);
+    std::uint64_t *d = out.store().dev_write(s, true);
+    chk(mhe_memcpy_d2d(eng, d, c, L * n * 8, s));
+    DevBuf t(eng, s, L * n), sp(eng, s, L * n);
+    chk(mhe_memcpy_d2d(eng, sp.p, sk, L * n * 8, s)); // s restricted to the level (first L limbs)
+    for (std::size_t k = 1; k < encrypted.size(); k++)
+    {
+        if (k > 1) chk(mhe_multiply_plain(eng, sp.p, sk, sp.p, 1, (int)L, s));
+        chk(mhe_multiply_plain(eng, c + k * L * n, sp.p, t.p, 1, (int)L, s));
+        chk(mhe_add(eng, d, t.p, d, 1, (int)L, s));
+    }
+    out.scale() = encrypted.scale();
+    destination = std::move(out);
+}
+} // namespace seal

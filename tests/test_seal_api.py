@@ -211,6 +211,21 @@ def test_seal_api_end_to_end():
     assert "0 failed" in r.stdout
 
 
+@pytest.mark.gpu
+def test_evaluator_behaviour_pinned():
+    """The Evaluator's observable behaviour at N = 2^12 (tests/cpp/seal_pin_test.cpp): every entry
+    point's exceptions (exact type and text, operands unchanged after the throw), every out-of-place
+    entry point against its in-place form under the four destination patterns, and the engine
+    operation counts and merge counters of one fixed script run directly, in a FiberBatch and in a
+    Lockstep group, as literals."""
+    _build()
+    r = subprocess.run([os.path.join(ROOT, "build", "seal_pin_test")], capture_output=True, text=True, timeout=300)
+    print(r.stdout)
+    print(r.stderr)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "ALL PASSED" in r.stdout and ", 0 failed" in r.stdout
+
+
 def _consumer(tmp):
     _build()
     bdir = os.path.join(tmp, "consumer")
