@@ -166,6 +166,39 @@ __global__ void k_mulplain_sum(SumPtrs P, int cnt, u64 *acc, int accumulate, con
     *(ulonglong2 *)(acc + i) = z;
 }
 
+// out = sum_k ct[k] * s^k (Decryptor::decrypt's dot product with the powers of the secret key) by
+// Horner over the polys, every intermediate reduced mod q_l: the residues of multiplying the powers
+// out and adding term by term.  sk is the key-level secret key, whose first `limbs` limbs lie at the
+// same offsets as a poly of the level; out may alias ct[0] (a lane reads its words before it writes).
+__global__ void k_decrypt(const u64 *ct, int size, const u64 *sk, u64 *out, const PrimeDev *primes, int limbs,
+                          int log_n, size_t total2, int fp)
+{
+    size_t i2 = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i2 >= total2) return;
+    const size_t i = i2 * 2;
+    const size_t ps = (size_t)limbs << log_n;
+    const PrimeDev p = primes[(int)(i >> log_n)];
+    const bool f = elem_fp(fp, p);
+    const ulonglong2 s = *(const ulonglong2 *)(sk + i);
+    ulonglong2 z = *(const ulonglong2 *)(ct + (size_t)(size - 1) * ps + i);
+    for (int k = size - 2; k >= 0; k--)
+    {
+        const ulonglong2 x = *(const ulonglong2 *)(ct + (size_t)k * ps + i);
+        if (f)
+        {
+            // canonical x (< q) + a product in (-1.25q, 1.25q): |.| < 2.25q, exact
+            z.x = fp_canon(fp_from_u52(x.x) + mulmod_fd(z.x, s.x, p), p.qd, p.qi);
+            z.y = fp_canon(fp_from_u52(x.y) + mulmod_fd(z.y, s.y, p), p.qd, p.qi);
+        }
+        else
+        {
+            z.x = addmod(x.x, mulmod(z.x, s.x, p), p.q);
+            z.y = addmod(x.y, mulmod(z.y, s.y, p), p.q);
+        }
+    }
+    *(ulonglong2 *)(out + i) = z;
+}
+
 struct ScalarTab
 {
     u64 v[64];

@@ -60,10 +60,19 @@ struct mhe_encoder
     struct DevRoots
     {
         int dev;
-        double2 *roots;
+        double2 *roots; // inv_root_powers [n], then root_powers [n] (decode's forward FFT)
+    };
+    // decode's RNS constants of one level (the first `q.size()` primes of a chain) on one device:
+    // Q, (Q+1)/2, (Q/q_j)^-1 mod q_j and the punctured products Q/q_j, W words each
+    struct DecLevel
+    {
+        int dev;
+        std::vector<uint64_t> q;
+        uint64_t *consts;
     };
     mutable std::mutex mu;
     mutable std::vector<DevRoots> dev_roots;
+    mutable std::vector<DecLevel> dec_levels;
     mutable double *ring = nullptr; // kRing slots of 2 * slots doubles (re, im), pinned
     mutable hipEvent_t ring_ev[kRing] = {};
     mutable int ring_dev = -1;
@@ -71,6 +80,7 @@ struct mhe_encoder
     ~mhe_encoder()
     {
         for (auto &d : dev_roots) (void)hipFree(d.roots);
+        for (auto &d : dec_levels) (void)hipFree(d.consts);
         if (ring) (void)hipHostFree(ring);
         for (auto &ev : ring_ev)
             if (ev) (void)hipEventDestroy(ev);
@@ -136,6 +146,31 @@ u64 words_mod(const u64 *w, int nw, u64 q)
     u128 r = 0;
     for (int k = nw - 1; k >= 0; k--) r = ((r << 64) | w[k]) % q;
     return (u64)r;
+}
+
+// The encoder's complex roots on device `dev`, uploaded once per device (caller holds e->mu):
+// inv_root_powers for encode's inverse FFT, root_powers behind them for decode's forward FFT.
+int device_roots(const mhe_encoder *e, int dev, const double2 **out)
+{
+    for (auto &d : e->dev_roots)
+        if (d.dev == dev)
+        {
+            *out = d.roots;
+            return MHE_OK;
+        }
+    const size_t n = e->n;
+    double2 *r = nullptr;
+    if (hipMalloc((void **)&r, 2 * n * sizeof(double2)) != hipSuccess)
+        return mhe_internal_fail(MHE_ERR_MEMORY, "encoder roots allocation failed");
+    if (hipMemcpy(r, e->inv_root_powers.data(), n * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(r + n, e->root_powers.data(), n * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess)
+    {
+        (void)hipFree(r);
+        return mhe_internal_fail(MHE_ERR_DEVICE, "encoder roots upload failed");
+    }
+    e->dev_roots.push_back({ dev, r });
+    *out = r;
+    return MHE_OK;
 }
 } // namespace
 
@@ -352,21 +387,7 @@ extern "C" __attribute__((visibility("default"))) int mhe_ckks_encode_at(mhe_ctx
 
     std::unique_lock<std::mutex> lk(e->mu);
     const double2 *roots = nullptr;
-    for (auto &d : e->dev_roots)
-        if (d.dev == dev) roots = d.roots;
-    if (!roots)
-    {
-        double2 *r = nullptr;
-        if (hipMalloc((void **)&r, n * sizeof(double2)) != hipSuccess)
-            return mhe_internal_fail(MHE_ERR_MEMORY, "encoder roots allocation failed");
-        if (hipMemcpy(r, e->inv_root_powers.data(), n * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess)
-        {
-            (void)hipFree(r);
-            return mhe_internal_fail(MHE_ERR_DEVICE, "encoder roots upload failed");
-        }
-        e->dev_roots.push_back({ dev, r });
-        roots = r;
-    }
+    if (int rc = device_roots(e, dev, &roots)) return rc;
     // staging: [cv: n double2][values: 2 * count doubles][max word]
     const size_t vwords = count * (im ? 2 : 1);
     char *buf = nullptr;
@@ -532,44 +553,24 @@ extern "C" __attribute__((visibility("default"))) int mhe_ckks_encode_scalar(mhe
 }
 
 // ------------------------------------------------------------------------------------ decode
-// CKKSEncoder::decode (ckks.h:644-761).  The inverse NTT runs on the GPU; CRT composition
-// (RNSBase::compose_array, util/rns.cpp:354-400 -- its result is the canonical value in
-// [0, Q), so any exact composition gives SEAL's words), the sparse-slot mask (ckks.h:704-713),
-// SEAL's word-by-word double conversion (ckks.h:715-753) and transform_to_rev
-// (util/dwthandler.h:94-190) run on the host in SEAL's operation order.
+// CKKSEncoder::decode (ckks.h:644-761), all of it on the device and stream-ordered, in SEAL's
+// operation order (this file is compiled with -ffp-contract=off, see the top):
+//   * the inverse NTT of a copy of the plaintext;
+//   * k_dec_compose: the sparse-slot mask (ckks.h:704-713), CRT composition
+//     (RNSBase::compose_array, util/rns.cpp:354-400 -- its result is the canonical value in
+//     [0, Q), so any exact composition gives SEAL's words; here sum_j [x_j (Q/q_j)^-1]_{q_j} Q/q_j
+//     reduced mod Q after every term) and SEAL's word-by-word double conversion (ckks.h:715-753).
+//     The multi-word accumulator lives in registers: the kernel is instantiated per word-count
+//     class W = 1, 2, 4, ..., 64 >= limbs with every word loop unrolled, and the constants are
+//     read with wave-uniform (scalar) loads;
+//   * DWTHandler::transform_to_rev (util/dwthandler.h:94-190) over double2 with root_powers: the
+//     first log_n - 12 stages (gap >= 4096) register-resident in one launch (k_dec_fft_head), the
+//     last 12 inside 4096-point blocks in LDS (k_dec_fft_block), k_dec_fft_stage as the fallback;
+//   * k_dec_gather: out[i] = res[index_map[i]] with the index map 5^i computed per slot.
+// The RNS constants of a level are built on the host once per (encoder, device, primes of the
+// level) and stay in device memory.
 namespace
 {
-void fft_to_rev(cd *values, int log_n, const cd *roots)
-{
-    const size_t n = size_t(1) << log_n;
-    size_t gap = n >> 1, m = 1;
-    for (; m < (n >> 1); m <<= 1)
-    {
-        size_t offset = 0;
-        for (size_t i = 0; i < m; i++)
-        {
-            const cd r = *++roots;
-            cd *x = values + offset, *y = x + gap;
-            for (size_t j = 0; j < gap; j++)
-            {
-                const cd u = *x, v = *y * r;
-                *x++ = u + v;
-                *y++ = u - v;
-            }
-            offset += gap << 1;
-        }
-        gap >>= 1;
-    }
-    for (size_t i = 0; i < m; i++)
-    {
-        const cd r = *++roots;
-        const cd u = values[0], v = values[1] * r;
-        values[0] = u + v;
-        values[1] = u - v;
-        values += 2;
-    }
-}
-
 // a (L words) * s -> out (L words, truncated: every product here is < Q)
 void mp_mul_scalar(const u64 *a, size_t L, u64 s, u64 *out)
 {
@@ -579,24 +580,6 @@ void mp_mul_scalar(const u64 *a, size_t L, u64 s, u64 *out)
         const u128 p = (u128)a[k] * s + carry;
         out[k] = (u64)p;
         carry = (u64)(p >> 64);
-    }
-}
-
-bool mp_geq(const u64 *a, const u64 *b, size_t L)
-{
-    for (size_t k = L; k-- > 0;)
-        if (a[k] != b[k]) return a[k] > b[k];
-    return true;
-}
-
-void mp_sub(u64 *a, const u64 *b, size_t L)
-{
-    u64 borrow = 0;
-    for (size_t k = 0; k < L; k++)
-    {
-        const u128 d = (u128)a[k] - b[k] - borrow;
-        a[k] = (u64)d;
-        borrow = (u64)(d >> 64) & 1;
     }
 }
 
@@ -615,132 +598,382 @@ u64 inv_mod(u64 a, u64 q)
     if (t < 0) t += q;
     return (u64)t;
 }
-} // namespace
 
-extern "C" __attribute__((visibility("default"))) int mhe_ckks_decode(mhe_ctx *c, const mhe_encoder *e,
-                                                                     const uint64_t *plain, int limbs, double scale,
-                                                                     size_t sparse_slots, double *re, double *im,
-                                                                     void *stream)
+// word-count class of a level: the smallest power of two >= limbs (limbs <= 64)
+int dec_words(int limbs)
 {
-    const PrimeDev *primes;
-    const uint64_t *q;
-    int K, log_n;
-    if (mhe_internal_primes(c, &primes, &q, &K, &log_n)) return mhe_internal_fail(MHE_ERR_ARG, "context is not valid");
-    if (!e || e->log_n != log_n) return mhe_internal_fail(MHE_ERR_ARG, "encoder does not match the context");
-    if (limbs < 1 || limbs > K || !plain) return mhe_internal_fail(MHE_ERR_ARG, "plain is not valid for encryption parameters");
-    if (!re) return mhe_internal_fail(MHE_ERR_ARG, "destination cannot be null");
-    if (!sparse_slots) sparse_slots = e->slots;
-    if (sparse_slots > e->slots || (sparse_slots & (sparse_slots - 1)))
-        return mhe_internal_fail(MHE_ERR_ARG, "sparse_slots must be a power of two <= slots");
-    if (scale <= 0 || static_cast<int>(std::log2(scale)) >= total_bits(q, limbs))
-        return mhe_internal_fail(MHE_ERR_ARG, "scale out of bounds");
-    const size_t n = e->n, L = (size_t)limbs;
-    hipStream_t st = (hipStream_t)stream;
+    int W = 1;
+    while (W < limbs) W <<= 1;
+    return W;
+}
 
-    std::vector<u64> x(n * L);
-    {
-        u64 *tmp = nullptr;
-        if (mhe_internal_alloc((void **)&tmp, n * L * sizeof(u64), st) != hipSuccess)
-            return mhe_internal_fail(MHE_ERR_MEMORY, "decode staging allocation failed");
-        hipError_t err = mhe_internal_copy_d2d(tmp, plain, n * L * sizeof(u64), st);
-        int rc = err == hipSuccess ? mhe_ntt_inverse(c, tmp, 1, limbs, 0, stream) : MHE_ERR_DEVICE;
-        if (rc == MHE_OK)
+// Device constants of the level q_0..q_{L-1} (caller holds e->mu), u64 words:
+// [Q: W][(Q+1)/2: W][(Q/q_j)^-1 mod q_j: L][Q/q_j: L x W], zero above a value's top word.
+int dec_level(const mhe_encoder *e, int dev, const uint64_t *q, int limbs, const u64 **out)
+{
+    const size_t L = (size_t)limbs, W = (size_t)dec_words(limbs);
+    for (auto &d : e->dec_levels)
+        if (d.dev == dev && d.q.size() == L && std::memcmp(d.q.data(), q, L * sizeof(u64)) == 0)
         {
-            err = hipMemcpyAsync(x.data(), tmp, n * L * sizeof(u64), hipMemcpyDeviceToHost, st);
-            if (err == hipSuccess) err = hipStreamSynchronize(st);
-            if (err != hipSuccess) rc = MHE_ERR_DEVICE;
+            *out = d.consts;
+            return MHE_OK;
         }
-        (void)mhe_internal_free(tmp, st);
-        if (rc != MHE_OK) return rc == MHE_ERR_DEVICE ? mhe_internal_fail(rc, "decode transfer failed") : rc;
-    }
-
-    // RNSBase constants: Q, Q/q_j, (Q/q_j)^{-1} mod q_j
-    std::vector<u64> Q(L, 0), punct(L * L, 0), inv_punct(L), tmp(L);
+    std::vector<u64> h(2 * W + L + L * W, 0), tmp(W);
+    u64 *Q = &h[0], *thr = &h[W], *inv_punct = &h[2 * W], *punct = &h[2 * W + L];
     Q[0] = 1;
     for (size_t j = 0; j < L; j++)
     {
-        mp_mul_scalar(Q.data(), L, q[j], tmp.data());
-        Q = tmp;
+        mp_mul_scalar(Q, W, q[j], tmp.data());
+        std::memcpy(Q, tmp.data(), W * sizeof(u64));
     }
     for (size_t j = 0; j < L; j++)
     {
-        u64 *p = &punct[j * L];
+        u64 *p = &punct[j * W];
         p[0] = 1;
         u64 pm = 1;
         for (size_t k = 0; k < L; k++)
         {
             if (k == j) continue;
-            mp_mul_scalar(p, L, q[k], tmp.data());
-            std::memcpy(p, tmp.data(), L * sizeof(u64));
+            mp_mul_scalar(p, W, q[k], tmp.data());
+            std::memcpy(p, tmp.data(), W * sizeof(u64));
             pm = (u64)(((u128)pm * (q[k] % q[j])) % q[j]);
         }
         inv_punct[j] = inv_mod(pm, q[j]);
     }
-    std::vector<u64> thr(Q);
+    std::memcpy(thr, Q, W * sizeof(u64));
+    thr[0] += 1; // Q is odd: no carry out of word 0
+    for (size_t k = 0; k < W; k++) thr[k] = (thr[k] >> 1) | (k + 1 < W ? thr[k + 1] << 63 : 0);
+    u64 *d = nullptr;
+    if (hipMalloc((void **)&d, h.size() * sizeof(u64)) != hipSuccess)
+        return mhe_internal_fail(MHE_ERR_MEMORY, "decode constants allocation failed");
+    if (hipMemcpy(d, h.data(), h.size() * sizeof(u64), hipMemcpyHostToDevice) != hipSuccess)
     {
-        thr[0] += 1; // Q is odd: no carry out of word 0
-        for (size_t k = 0; k < L; k++) thr[k] = (thr[k] >> 1) | (k + 1 < L ? thr[k + 1] << 63 : 0);
+        (void)hipFree(d);
+        return mhe_internal_fail(MHE_ERR_DEVICE, "decode constants upload failed");
     }
-    const size_t sparsity = e->slots / sparse_slots;
-    const double two64 = std::pow(2.0, 64), inv_scale = 1.0 / scale;
-    std::vector<cd> res(n);
-    std::vector<u64> acc(L);
-    for (size_t i = 0; i < n; i++)
+    e->dec_levels.push_back({ dev, std::vector<uint64_t>(q, q + L), d });
+    *out = d;
+    return MHE_OK;
+}
+
+// cv[i] = (double(centred CRT value of coefficient i) / scale, 0), or exactly 0 under the sparse
+// mask; x: coefficient-form residues [L][n], canonical.
+template <int W>
+__global__ __launch_bounds__(256) void k_dec_compose(const u64 *x, const u64 *consts, const PrimeDev *primes,
+                                                     double2 *cv, int L, int log_n, size_t sparsity, double inv_scale)
+{
+    const size_t n = (size_t)1 << log_n, i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    if (sparsity > 1 && ((i - 1) & (sparsity - 1)) != sparsity - 1) // i = 0 wraps, as in SEAL
     {
-        if (sparsity > 1 && ((i - 1) & (sparsity - 1)) != sparsity - 1)
+        cv[i] = double2{ 0.0, 0.0 };
+        return;
+    }
+    const const_u64_p Q = (const_u64_p)consts, thr = Q + W, inv_punct = Q + 2 * W, punct = inv_punct + L;
+    u64 acc[W];
+    if (W == 1)
+        acc[0] = x[i];
+    else
+    {
+#pragma unroll
+        for (int k = 0; k < W; k++) acc[k] = 0;
+        for (int j = 0; j < L; j++)
         {
-            res[i] = 0.0;
-            continue;
-        }
-        if (L == 1)
-            acc[0] = x[i];
-        else
-        {
-            std::fill(acc.begin(), acc.end(), 0);
-            for (size_t j = 0; j < L; j++)
+            const PrimeDev p = prime_at(primes, j);
+            const u64 t = mulmod(x[(size_t)j * n + i], inv_punct[j], p);
+            const const_u64_p pj = punct + (size_t)j * W;
+            // acc += (Q/q_j) * t: both below Q, so the sum is below 2Q (one carry bit above W words)
+            u64 carry = 0;
+#pragma unroll
+            for (int k = 0; k < W; k++)
             {
-                const u64 t = (u64)(((u128)x[j * n + i] * inv_punct[j]) % q[j]);
-                mp_mul_scalar(&punct[j * L], L, t, tmp.data());
-                u64 carry = 0;
-                for (size_t k = 0; k < L; k++)
-                {
-                    const u128 s = (u128)acc[k] + tmp[k] + carry;
-                    acc[k] = (u64)s;
-                    carry = (u64)(s >> 64);
-                }
-                if (carry || mp_geq(acc.data(), Q.data(), L)) mp_sub(acc.data(), Q.data(), L);
+                u64 lo, hi;
+                mul128(pj[k], t, lo, hi);
+                u64 s = acc[k] + lo;
+                u64 cy = s < lo;
+                s += carry;
+                cy += s < carry;
+                acc[k] = s;
+                carry = hi + cy;
+            }
+            // acc -= Q when acc >= Q
+            u64 borrow = 0;
+#pragma unroll
+            for (int k = 0; k < W; k++)
+            {
+                const u64 qk = Q[k];
+                borrow = (acc[k] < qk) | ((acc[k] == qk) & borrow);
+            }
+            const u64 mask = (carry | (borrow ^ 1)) ? ~(u64)0 : 0;
+            borrow = 0;
+#pragma unroll
+            for (int k = 0; k < W; k++)
+            {
+                const u64 qk = Q[k] & mask;
+                const u64 d = acc[k] - qk, b1 = acc[k] < qk;
+                acc[k] = d - borrow;
+                borrow = b1 | (d < borrow);
             }
         }
-        double v = 0.0, s64 = inv_scale;
-        if (mp_geq(acc.data(), thr.data(), L))
-        {
-            for (size_t j = 0; j < L; j++, s64 *= two64)
+    }
+    // ckks.h:715-753: negative when acc >= (Q+1)/2; every word in turn, zero words skipped
+    u64 below = 0;
+#pragma unroll
+    for (int k = 0; k < W; k++)
+    {
+        const u64 tk = thr[k];
+        below = (acc[k] < tk) | ((acc[k] == tk) & below);
+    }
+    double v = 0.0, s64 = inv_scale;
+    if (!below)
+    {
+#pragma unroll
+        for (int k = 0; k < W; k++)
+            if (k < L)
             {
-                if (acc[j] > Q[j])
+                const u64 qk = Q[k];
+                if (acc[k] > qk)
                 {
-                    const u64 diff = acc[j] - Q[j];
+                    const u64 diff = acc[k] - qk;
                     v += diff ? static_cast<double>(diff) * s64 : 0.0;
                 }
                 else
                 {
-                    const u64 diff = Q[j] - acc[j];
+                    const u64 diff = qk - acc[k];
                     v -= diff ? static_cast<double>(diff) * s64 : 0.0;
                 }
+                s64 *= 0x1p64;
             }
-        }
-        else
-        {
-            for (size_t j = 0; j < L; j++, s64 *= two64)
-                v += acc[j] ? static_cast<double>(acc[j]) * s64 : 0.0;
-        }
-        res[i] = cd(v, 0.0);
     }
-    fft_to_rev(res.data(), log_n, e->root_powers.data());
+    else
+    {
+#pragma unroll
+        for (int k = 0; k < W; k++)
+            if (k < L)
+            {
+                v += acc[k] ? static_cast<double>(acc[k]) * s64 : 0.0;
+                s64 *= 0x1p64;
+            }
+    }
+    cv[i] = double2{ v, 0.0 };
+}
+
+// one butterfly of transform_to_rev: u = x, v = y * r, x = u + v, y = u - v, the complex product
+// as (ac - bd, ad + bc) (no contraction)
+__device__ __forceinline__ void dec_bfly(double2 &x, double2 &y, double2 r)
+{
+    const double2 u = x, v = double2{ y.x * r.x - y.y * r.y, y.x * r.y + y.y * r.x };
+    x = double2{ u.x + v.x, u.y + v.y };
+    y = double2{ u.x - v.x, u.y - v.y };
+}
+
+// Stage s of transform_to_rev has m = 2^s groups of gap n >> (s + 1); group g uses roots[m + g].
+
+// stages 0 .. LR-1 (gap n/2 .. 2^lb, LR = log_n - lb) in one launch: they only pair elements with the
+// same low lb bits, so a lane holds the 2^LR <= 16 elements of one such column in registers and runs
+// the stages in order (the counterpart of k_enc_fft_tail)
+template <int LR>
+__global__ __launch_bounds__(256) void k_dec_fft_head(double2 *cv, const double2 *roots, int lb)
+{
+    constexpr int R = 1 << LR;
+    const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= ((size_t)1 << lb)) return;
+    double2 v[R];
+#pragma unroll
+    for (int j = 0; j < R; j++) v[j] = cv[c + ((size_t)j << lb)];
+#pragma unroll
+    for (int s = 0; s < LR; s++)
+    {
+        const int h = R >> (s + 1); // the stage's gap in column elements
+#pragma unroll
+        for (int j = 0; j < R; j++)
+            if (!(j & h)) dec_bfly(v[j], v[j + h], roots[((size_t)1 << s) + (size_t)(j >> (LR - s))]);
+    }
+#pragma unroll
+    for (int j = 0; j < R; j++) cv[c + ((size_t)j << lb)] = v[j];
+}
+
+// stages log_n-lb .. log_n-1 (gap 2^(lb-1) .. 1) of one 2^lb-point block in LDS (the counterpart
+// of k_enc_fft_block)
+__global__ __launch_bounds__(256) void k_dec_fft_block(double2 *cv, const double2 *roots, int log_n, int lb)
+{
+    __shared__ double2 sh[1 << kEncLogBlock];
+    const size_t B = (size_t)1 << lb, base = (size_t)blockIdx.x << lb;
+    for (size_t t = threadIdx.x; t < B; t += 256) sh[t] = cv[base + t];
+    __syncthreads();
+    for (int s2 = 0; s2 < lb; s2++)
+    {
+        const int sh_k = lb - 1 - s2; // log2 of the stage's gap
+        const size_t gap = (size_t)1 << sh_k;
+        const size_t first = ((size_t)1 << (log_n - lb + s2)) + ((size_t)blockIdx.x << s2); // root of the block's group 0
+        for (size_t t = threadIdx.x; t < B / 2; t += 256)
+        {
+            const size_t k = t >> sh_k, xi = (k << (sh_k + 1)) + (t & (gap - 1));
+            dec_bfly(sh[xi], sh[xi + gap], roots[first + k]);
+        }
+        __syncthreads();
+    }
+    for (size_t t = threadIdx.x; t < B; t += 256) cv[base + t] = sh[t];
+}
+
+// one stage s over the whole vector
+__global__ void k_dec_fft_stage(double2 *cv, const double2 *roots, int log_n, int s)
+{
+    const size_t n = (size_t)1 << log_n, t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n / 2) return;
+    const int sh_k = log_n - 1 - s;
+    const size_t gap = (size_t)1 << sh_k, k = t >> sh_k, xi = (k << (sh_k + 1)) + (t & (gap - 1));
+    dec_bfly(cv[xi], cv[xi + gap], roots[((size_t)1 << s) + k]);
+}
+
+// out[i] = cv[index_map[i]], index_map[i] = rev((5^i mod 2n - 1) / 2) (ckks.cpp:34-49)
+__global__ void k_dec_gather(const double2 *cv, double2 *out, size_t count, int log_n)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    const u64 m = (u64)2 << log_n;
+    u64 pos = 1, b = 5;
+    for (u64 e = i; e; e >>= 1)
+    {
+        if (e & 1) pos = (pos * b) & (m - 1);
+        b = (b * b) & (m - 1);
+    }
+    out[i] = cv[rev_bits_dev((u32)((pos - 1) >> 1), log_n)];
+}
+
+struct DecodeCtx
+{
+    const PrimeDev *primes;
+    const uint64_t *q;
+    int K, log_n;
+};
+
+// the argument checks of CKKSEncoder::decode; *sparse_slots 0 becomes n/2
+int decode_check(mhe_ctx *c, const mhe_encoder *e, const uint64_t *plain, int limbs, double scale,
+                 size_t *sparse_slots, const void *dest, DecodeCtx *d)
+{
+    if (mhe_internal_primes(c, &d->primes, &d->q, &d->K, &d->log_n))
+        return mhe_internal_fail(MHE_ERR_ARG, "context is not valid");
+    if (!e || e->log_n != d->log_n) return mhe_internal_fail(MHE_ERR_ARG, "encoder does not match the context");
+    if (limbs < 1 || limbs > d->K || !plain)
+        return mhe_internal_fail(MHE_ERR_ARG, "plain is not valid for encryption parameters");
+    if (!dest) return mhe_internal_fail(MHE_ERR_ARG, "destination cannot be null");
+    if (!*sparse_slots) *sparse_slots = e->slots;
+    if (*sparse_slots > e->slots || (*sparse_slots & (*sparse_slots - 1)))
+        return mhe_internal_fail(MHE_ERR_ARG, "sparse_slots must be a power of two <= slots");
+    if (scale <= 0 || static_cast<int>(std::log2(scale)) >= total_bits(d->q, limbs))
+        return mhe_internal_fail(MHE_ERR_ARG, "scale out of bounds");
+    return MHE_OK;
+}
+
+// checked arguments -> out_dev[sparse_slots] (re, im), enqueued on st
+int decode_run(mhe_ctx *c, const mhe_encoder *e, const DecodeCtx &d, const uint64_t *plain, int limbs, double scale,
+               size_t sparse_slots, double *out_dev, hipStream_t st)
+{
+    const size_t n = e->n, L = (size_t)limbs;
+    const int log_n = d.log_n;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return mhe_internal_fail(MHE_ERR_DEVICE, "no device");
+    const double2 *roots = nullptr;
+    const u64 *consts = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(e->mu);
+        if (int rc = device_roots(e, dev, &roots)) return rc;
+        if (int rc = dec_level(e, dev, d.q, limbs, &consts)) return rc;
+    }
+    roots += n; // root_powers
+    // staging: [x: L * n words][cv: n double2]
+    char *buf = nullptr;
+    if (mhe_internal_alloc((void **)&buf, n * L * sizeof(u64) + n * sizeof(double2), st) != hipSuccess)
+        return mhe_internal_fail(MHE_ERR_MEMORY, "decode staging allocation failed");
+    u64 *x = (u64 *)buf;
+    double2 *cv = (double2 *)(x + n * L);
+    hipError_t err = mhe_internal_copy_d2d(x, plain, n * L * sizeof(u64), st);
+    int rc = err == hipSuccess ? mhe_ntt_inverse(c, x, 1, limbs, 0, st) : MHE_OK;
+    if (err == hipSuccess && rc == MHE_OK)
+    {
+        const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+        const size_t sparsity = e->slots / sparse_slots;
+        const double inv_scale = 1.0 / scale;
+        switch (dec_words(limbs))
+        {
+#define MHE_DEC_COMPOSE(w)                                                                                           \
+    case w:                                                                                                          \
+        hipLaunchKernelGGL(k_dec_compose<w>, grid, block, 0, st, x, consts, d.primes, cv, limbs, log_n, sparsity,    \
+                           inv_scale);                                                                               \
+        break;
+            MHE_DEC_COMPOSE(1)
+            MHE_DEC_COMPOSE(2)
+            MHE_DEC_COMPOSE(4)
+            MHE_DEC_COMPOSE(8)
+            MHE_DEC_COMPOSE(16)
+            MHE_DEC_COMPOSE(32)
+            MHE_DEC_COMPOSE(64)
+#undef MHE_DEC_COMPOSE
+        }
+        const int lb = std::min(log_n, kEncLogBlock);
+        const dim3 hg((unsigned)(((1u << lb) + 255) / 256));
+        if (log_n - lb == 4)
+            hipLaunchKernelGGL(k_dec_fft_head<4>, hg, block, 0, st, cv, roots, lb);
+        else if (log_n - lb == 3)
+            hipLaunchKernelGGL(k_dec_fft_head<3>, hg, block, 0, st, cv, roots, lb);
+        else if (log_n - lb == 2)
+            hipLaunchKernelGGL(k_dec_fft_head<2>, hg, block, 0, st, cv, roots, lb);
+        else if (log_n - lb == 1)
+            hipLaunchKernelGGL(k_dec_fft_head<1>, hg, block, 0, st, cv, roots, lb);
+        else
+            for (int s = 0; s < log_n - lb; s++)
+                hipLaunchKernelGGL(k_dec_fft_stage, dim3((unsigned)((n / 2 + 255) / 256)), block, 0, st, cv, roots, log_n,
+                                   s);
+        hipLaunchKernelGGL(k_dec_fft_block, dim3((unsigned)(n >> lb)), block, 0, st, cv, roots, log_n, lb);
+        hipLaunchKernelGGL(k_dec_gather, dim3((unsigned)((sparse_slots + 255) / 256)), block, 0, st, cv,
+                           (double2 *)out_dev, sparse_slots, log_n);
+        err = hipGetLastError();
+    }
+    (void)mhe_internal_free(buf, st);
+    if (rc != MHE_OK) return rc;
+    if (err != hipSuccess) return mhe_internal_fail(MHE_ERR_DEVICE, hipGetErrorString(err));
+    return MHE_OK;
+}
+} // namespace
+
+extern "C" __attribute__((visibility("default"))) int mhe_ckks_decode_dev(mhe_ctx *c, const mhe_encoder *e,
+                                                                         const uint64_t *plain, int limbs,
+                                                                         double scale, size_t sparse_slots,
+                                                                         double *out_dev, void *stream)
+{
+    DecodeCtx d;
+    if (int rc = decode_check(c, e, plain, limbs, scale, &sparse_slots, out_dev, &d)) return rc;
+    return decode_run(c, e, d, plain, limbs, scale, sparse_slots, out_dev, (hipStream_t)stream);
+}
+
+// mhe_ckks_decode_dev, then one download of the sparse_slots complex values
+extern "C" __attribute__((visibility("default"))) int mhe_ckks_decode(mhe_ctx *c, const mhe_encoder *e,
+                                                                     const uint64_t *plain, int limbs, double scale,
+                                                                     size_t sparse_slots, double *re, double *im,
+                                                                     void *stream)
+{
+    DecodeCtx d;
+    if (int rc = decode_check(c, e, plain, limbs, scale, &sparse_slots, re, &d)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    double *out = nullptr;
+    if (mhe_internal_alloc((void **)&out, 2 * sparse_slots * sizeof(double), st) != hipSuccess)
+        return mhe_internal_fail(MHE_ERR_MEMORY, "decode staging allocation failed");
+    std::vector<double> z(2 * sparse_slots);
+    int rc = decode_run(c, e, d, plain, limbs, scale, sparse_slots, out, st);
+    if (rc == MHE_OK)
+    {
+        hipError_t err = hipMemcpyAsync(z.data(), out, z.size() * sizeof(double), hipMemcpyDeviceToHost, st);
+        if (err == hipSuccess) err = hipStreamSynchronize(st);
+        if (err != hipSuccess) rc = mhe_internal_fail(MHE_ERR_DEVICE, "decode transfer failed");
+    }
+    (void)mhe_internal_free(out, st);
+    if (rc != MHE_OK) return rc;
     for (size_t i = 0; i < sparse_slots; i++)
     {
-        const cd z = res[e->index_map[i]];
-        re[i] = z.real();
-        if (im) im[i] = z.imag();
+        re[i] = z[2 * i];
+        if (im) im[i] = z[2 * i + 1];
     }
     return MHE_OK;
 }
+

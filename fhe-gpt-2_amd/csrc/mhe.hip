@@ -1892,6 +1892,25 @@ MHE_EXPORT int mhe_multiply_plain_sum(mhe_ctx *c, int count, const uint64_t *con
     return MHE_OK;
 }
 
+MHE_EXPORT int mhe_decrypt(mhe_ctx *c, const uint64_t *ct, int size, const uint64_t *sk, uint64_t *out, int limbs,
+                           void *s)
+{
+    TR("out", out, 1, limbs); TR("ct", ct, size, limbs); TR("sk", sk, 1, limbs);
+    TRC(0, 0, 0, 0);
+    int r = check_poly_args(c, ct, size, limbs);
+    if (r) return r;
+    if (size < 2 || !sk || !out) return fail(MHE_ERR_ARG, "invalid polynomial arguments");
+    // the op mix of the sequence this replaces: s^2..s^(size-1) and the size - 1 products c_k s^k
+    // as plaintext products, and size - 1 additions
+    count_op(c, MHE_OPK_MULPLAIN, limbs, (unsigned long long)(2 * size - 3));
+    count_op(c, MHE_OPK_ADDSUB, limbs, (unsigned long long)(size - 1));
+    const size_t total2 = ((size_t)limbs << c->log_n) / 2;
+    hipLaunchKernelGGL(k_decrypt, ELEM_GRID(total2), dim3(256), 0, S(s), ct, size, sk, out, c->primes, limbs, c->log_n,
+                       total2, c->nm.fp ? 1 : 0);
+    HIP_LAUNCH_CHECK();
+    return MHE_OK;
+}
+
 // op 2 (set): a is out.  The table is copied into the descriptor once limbs is known to be in range.
 static int launch_scalar(mhe_ctx *c, const u64 *a, const u64 *scalars, u64 *out, int polys, int limbs, int op,
                          void *s)

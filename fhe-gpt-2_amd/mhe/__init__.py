@@ -105,6 +105,8 @@ SIGNATURES = {
                                           ctypes.c_size_t, ctypes.c_double, ctypes.c_int, ctypes.c_int, vp, vp]),
     "mhe_ckks_decode": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.c_double, ctypes.c_size_t,
                                        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), vp]),
+    "mhe_ckks_decode_dev": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.c_double, ctypes.c_size_t, vp, vp]),
+    "mhe_decrypt": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, vp, ctypes.c_int, vp]),
     "mhe_ckks_encode_scalar_at": (ctypes.c_int, [vp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int,
                                                  u64p]),
     "mhe_prng_uniform_bulk": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_uint32, vp]),
@@ -577,6 +579,28 @@ class Engine:
         _check(lib().mhe_ckks_decode(self._h, self._encoder(), _ptr(plain), limbs, scale, sparse_slots,
                                      re.ctypes.data_as(dp), im.ctypes.data_as(dp), self.stream()))
         return re + 1j * im
+
+    def decode_dev(self, plain, scale, sparse_slots=0, out=None):
+        """CKKSEncoder::decode with the slots left on the device: a torch.complex128 tensor of
+        sparse_slots (0 = n/2) values, enqueued on the current stream (no host synchronisation)."""
+        torch = _torch()
+        limbs = plain.shape[-2]
+        cnt = sparse_slots or self.n // 2
+        if out is None:
+            out = torch.empty(cnt, dtype=torch.complex128, device=self.torch_device)
+        elif out.dtype != torch.complex128 or out.numel() != cnt or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError("out must be a contiguous complex128 device tensor of sparse_slots values")
+        _check(lib().mhe_ckks_decode_dev(self._h, self._encoder(), _ptr(plain), limbs, scale, sparse_slots, _ptr(out),
+                                         self.stream()))
+        return out
+
+    def decrypt(self, ct, sk, out=None):
+        """Decryptor::decrypt: ct [size][limbs][n] and the key-level NTT-form secret key sk [K][n] ->
+        the NTT-form plaintext [limbs][n] = sum_k ct[k] * s^k.  `out` may be ct[0]."""
+        size, limbs = ct.shape[0], ct.shape[1]
+        out = self.empty(limbs, self.n) if out is None else out
+        _check(lib().mhe_decrypt(self._h, _ptr(ct), size, _ptr(sk), _ptr(out), limbs, self.stream()))
+        return out
 
     def encode_scalar(self, value, scale, limbs, bound_limbs=None):
         out = (ctypes.c_uint64 * limbs)()

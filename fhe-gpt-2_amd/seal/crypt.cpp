@@ -97,12 +97,16 @@ void CKKSEncoder::decode_internal(const Plaintext &plain, std::vector<std::compl
     auto cd = ctx_.get_context_data(plain.parms_id());
     if (!cd) throw std::invalid_argument("plain is not valid for encryption parameters");
     const std::size_t L = cd->parms().coeff_modulus().size();
-    std::vector<double> re(sparse_slots_), im(sparse_slots_);
+    mhe_ctx *eng = ctx_.engine();
     void *s = ctx_.stream();
-    chk(mhe_ckks_decode(ctx_.engine(), enc_, plain.store().dev_read(s), (int)L, plain.scale(),
-                        sparse_slots_ == slots_ ? 0 : sparse_slots_, re.data(), im.data(), s));
+    // the slots are decoded on the device as interleaved (re, im) doubles -- complex<double>'s
+    // layout -- and downloaded straight into the destination
+    DevBuf z(eng, s, 2 * sparse_slots_);
+    chk(mhe_ckks_decode_dev(eng, enc_, plain.store().dev_read(s), (int)L, plain.scale(),
+                            sparse_slots_ == slots_ ? 0 : sparse_slots_, reinterpret_cast<double *>(z.p), s));
     out.resize(sparse_slots_);
-    for (std::size_t i = 0; i < sparse_slots_; i++) out[i] = { re[i], im[i] };
+    chk(mhe_memcpy_d2h(eng, out.data(), z.p, sparse_slots_ * sizeof(std::complex<double>), s));
+    chk(mhe_stream_sync(eng, s));
 }
 
 void CKKSEncoder::decode(const Plaintext &plain, std::vector<std::complex<double>> &destination, MemoryPoolHandle)
@@ -302,7 +306,7 @@ void Decryptor::decrypt(const Ciphertext &encrypted, Plaintext &destination)
     auto cd = ctx_.get_context_data(encrypted.parms_id());
     if (!cd || encrypted.size() < 2) throw std::invalid_argument("encrypted is not valid for encryption parameters");
     if (!encrypted.is_ntt_form()) throw std::invalid_argument("encrypted must be in NTT form");
-    const std::size_t L = cd->parms().coeff_modulus().size(), n = cd->parms().poly_modulus_degree();
+    const std::size_t L = cd->parms().coeff_modulus().size();
     mhe_ctx *eng = ctx_.engine();
     void *s = ctx_.stream();
     const std::uint64_t *c = encrypted.store().dev_read(s);
@@ -310,15 +314,7 @@ void Decryptor::decrypt(const Ciphertext &encrypted, Plaintext &destination)
     Plaintext out;
     out.set_level(ctx_, encrypted.parms_id(), L);
     std::uint64_t *d = out.store().dev_write(s, true);
-    chk(mhe_memcpy_d2d(eng, d, c, L * n * 8, s));
-    DevBuf t(eng, s, L * n), sp(eng, s, L * n);
-    chk(mhe_memcpy_d2d(eng, sp.p, sk, L * n * 8, s)); // s restricted to the level (first L limbs)
-    for (std::size_t k = 1; k < encrypted.size(); k++)
-    {
-        if (k > 1) chk(mhe_multiply_plain(eng, sp.p, sk, sp.p, 1, (int)L, s));
-        chk(mhe_multiply_plain(eng, c + k * L * n, sp.p, t.p, 1, (int)L, s));
-        chk(mhe_add(eng, d, t.p, d, 1, (int)L, s));
-    }
+    chk(mhe_decrypt(eng, c, (int)encrypted.size(), sk, d, (int)L, s));
     out.scale() = encrypted.scale();
     destination = std::move(out);
 }

@@ -212,6 +212,13 @@ int mhe_add_scalar(mhe_ctx *ctx, const uint64_t *a, const uint64_t *scalars, uin
  * ckks.cpp:78-200, writes the same residue into every coefficient of limb l). */
 int mhe_set_scalar(mhe_ctx *ctx, const uint64_t *scalars, uint64_t *out, int polys, int limbs, void *stream);
 
+/* Decryptor::decrypt (decryptor.cpp, ckks_decrypt): out[L][n] = sum_k ct[k] * s^k over the
+ * first `limbs` limbs of the NTT-form secret key sk (key level, limb-major); size >= 2.  One pass
+ * (Horner over the polys, every intermediate reduced mod q_l); out may alias ct[0].  Counted in
+ * mhe_op_counts as the 2 * size - 3 plaintext products and size - 1 additions it stands for. */
+int mhe_decrypt(mhe_ctx *ctx, const uint64_t *ct, int size, const uint64_t *sk, uint64_t *out, int limbs,
+                void *stream);
+
 /* ---- ciphertext ops -------------------------------------------------------------------
  * Evaluator::ckks_multiply, size-2 x size-2 (evaluator.cpp:673-773): out3 = [3][L][n]. */
 int mhe_ct_multiply(mhe_ctx *ctx, const uint64_t *a, const uint64_t *b, uint64_t *out3, int limbs, void *stream);
@@ -323,8 +330,9 @@ int mhe_hmult_batch(mhe_ctx *ctx, int count, const uint64_t *const *a, const uin
 
 /* ---- CKKS encoding (SEAL/ckks.cpp:10-200, SEAL/ckks.h:457-640) ---------------------------
  * An encoder holds CKKSEncoder's constructor tables (index map 5^i, complex roots).  Encoding
- * is SEAL's host double-precision FFT in SEAL's operation order (no FMA, bit-identical),
- * then the RNS reduction and the per-limb NTT on the GPU. */
+ * is SEAL's double-precision FFT in SEAL's operation order (no FMA, bit-identical), then the
+ * RNS reduction and the per-limb NTT; decoding is the inverse NTT, the CRT composition, SEAL's
+ * double conversion and its forward FFT.  Both run on the GPU. */
 typedef struct mhe_encoder mhe_encoder;
 int mhe_encoder_create(mhe_encoder **enc, int log_n);
 int mhe_encoder_destroy(mhe_encoder *enc);
@@ -345,9 +353,17 @@ int mhe_ckks_encode_at(mhe_ctx *ctx, const mhe_encoder *enc, const double *re, c
                        double scale, int bound_limbs, int limbs, uint64_t *out_dev, void *stream);
 /* CKKSEncoder::decode (ckks.h:644-761): NTT-form plaintext [limbs][n] on the device ->
  * `sparse_slots` slot values (0 = n/2; the modified SEAL's sparse decode, ckks.h:704-713).
- * `im` may be NULL (decode to vector<double>).  Synchronous on `stream`. */
+ * `im` may be NULL (decode to vector<double>).  Synchronous on `stream`: mhe_ckks_decode_dev
+ * followed by one download of the slot values. */
 int mhe_ckks_decode(mhe_ctx *ctx, const mhe_encoder *enc, const uint64_t *plain_dev, int limbs, double scale,
                     size_t sparse_slots, double *re, double *im, void *stream);
+/* CKKSEncoder::decode with the result left on the device: out_dev receives sparse_slots
+ * (0 = n/2) complex values, interleaved (re, im) doubles.  Stream-ordered, no host
+ * synchronisation, no allocation after the first call of a (context, limbs, stream).  The whole
+ * decode runs on the GPU in SEAL's operation order: inverse NTT, CRT composition with the sparse
+ * mask and the word-by-word double conversion, DWTHandler::transform_to_rev, slot gather. */
+int mhe_ckks_decode_dev(mhe_ctx *ctx, const mhe_encoder *enc, const uint64_t *plain_dev, int limbs,
+                        double scale, size_t sparse_slots, double *out_dev, void *stream);
 int mhe_ckks_encode_scalar_at(mhe_ctx *ctx, double value, double scale, int bound_limbs, int limbs,
                               uint64_t *residues);
 

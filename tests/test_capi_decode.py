@@ -1,0 +1,48 @@
+"""CPU-side checks of the device decode / decrypt entry points (no GPU compute): libmhe.so exports
+mhe_ckks_decode_dev and mhe_decrypt, the Python binding declares them, and both answer a null
+context with MHE_ERR_ARG."""
+import ctypes
+import json
+import subprocess
+import sys
+
+import mhe
+
+NEW_ENTRY_POINTS = ["mhe_ckks_decode_dev", "mhe_decrypt"]
+
+_NULL_CTX_CHILD = """
+import ctypes, json, sys
+lib = ctypes.CDLL(sys.argv[1])
+kinds = {"p": ctypes.c_void_p, "i": ctypes.c_int, "d": ctypes.c_double, "z": ctypes.c_size_t}
+for name, sig in json.loads(sys.argv[2]):
+    f = getattr(lib, name)
+    f.restype = ctypes.c_int
+    f.argtypes = [kinds[k] for k in sig]
+    rc = f(*[kinds[k](0) for k in sig])
+    print(name, rc, flush=True)
+"""
+
+
+def test_library_exports_decode_dev_and_decrypt():
+    lib = ctypes.CDLL(mhe.LIB_PATH)
+    for name in NEW_ENTRY_POINTS:
+        assert hasattr(lib, name), name
+        assert name in mhe.SIGNATURES, name
+    assert hasattr(mhe.Engine, "decode_dev") and hasattr(mhe.Engine, "decrypt")
+
+
+def test_null_context_is_an_argument_error():
+    """A fresh child process that only loads the library calls each new entry point with a null
+    context and every other argument zero: MHE_ERR_ARG, nothing read through the context, no GPU
+    opened."""
+    codes = {ctypes.c_int: "i", ctypes.c_double: "d", ctypes.c_size_t: "z", ctypes.c_void_p: "p"}
+    sigs = []
+    for name in NEW_ENTRY_POINTS:
+        res, args = mhe.SIGNATURES[name]
+        assert res is ctypes.c_int
+        sigs.append((name, "".join(codes[t] for t in args)))
+    p = subprocess.run([sys.executable, "-c", _NULL_CTX_CHILD, mhe.LIB_PATH, json.dumps(sigs)],
+                       capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, (p.returncode, p.stdout, p.stderr)
+    got = [line.split() for line in p.stdout.splitlines()]
+    assert got == [[name, "-1"] for name in NEW_ENTRY_POINTS], (got, p.stderr)
