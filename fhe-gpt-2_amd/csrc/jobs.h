@@ -1,7 +1,7 @@
 // Job descriptors of the NTT passes (ntt.h): a job maps the launch's job index y to a view -- the
 // source and destination of one limb, its prime and twiddles, and the load / store that fuse the
 // step's arithmetic (lifts, epilogues) into the transform.  Kernel arguments, filled on the host by
-// the pipelines of mhe.hip.
+// the pipelines of keyswitch.h and rotate.h.
 #pragma once
 
 // A batch of jobs of one kind: entry e owns job indices [e * per, (e + 1) * per) of the launch and

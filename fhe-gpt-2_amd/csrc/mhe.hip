@@ -9,9 +9,11 @@
 //   invq[K][K]       (q_j^-1 mod q_i, Shoup)            -- RNSTool::inv_q_last_mod_q for every j
 // Scratch workspaces are per stream (see Workspace).
 //
-// This file holds the context, the pipelines and the C ABI; it is the one translation unit of
-// mhe.o and includes the NTT (ntt.h), hoisting (hoist.h), job descriptors (jobs.h), elementwise
-// kernels (elem.h) and the device allocator (devalloc.h) once each.
+// This file holds the errors, the host number theory, the context and workspace, the elementwise
+// path, the job builders and the C ABI; it is the one translation unit of mhe.o and includes the NTT
+// (ntt.h), hoisting (hoist.h), job descriptors (jobs.h), elementwise kernels (elem.h) and the device
+// allocator (devalloc.h) once each, and further down, where what they build on is defined, the
+// key-switch and rescale pipelines (keyswitch.h) and the rotation pipelines (rotate.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -203,11 +205,7 @@ struct Workspace
     int entries = 0;      // batch entries the scratch is sized for (<= MHE_MAXB)
     Scratch base;
     WsEntry e[MHE_MAXB];
-    u64 *coeff = nullptr; // entry 0's buffers under their old names
-    u64 *modup = nullptr;
-    u64 *acc = nullptr;
     u64 *tmp = nullptr;   // [L][n]        permuted c1 for Galois
-    u64 *ct3 = nullptr;   // [3][L][n]     tensor output for hmult
     // hoisted rotations (hoist.h): the ModUp of up to MHE_MAXB inputs, [K][K-1][n] each, and one
     // zero-coefficient flag per input
     Scratch hoist_base;
@@ -436,11 +434,7 @@ static int get_ws(mhe_ctx *c, hipStream_t st, int limbs, Workspace **out, int en
             w.e[i].acc = w.e[i].modup + (L + 1) * L * n;
             w.e[i].ct3 = w.e[i].acc + 2 * (L + 1) * n;
         }
-        w.coeff = w.e[0].coeff;
-        w.modup = w.e[0].modup;
-        w.acc = w.e[0].acc;
         w.tmp = w.base.p + (size_t)E * per;
-        w.ct3 = w.e[0].ct3;
         w.max_limbs = (int)L;
         w.entries = E;
     }
@@ -472,6 +466,23 @@ static int check_limbs(mhe_ctx *c, int limbs, int lo)
 static bool ranges_overlap(const u64 *a, size_t aw, const u64 *b, size_t bw)
 {
     return a < b + bw && b < a + aw;
+}
+
+// Does output i (ow words) share a word with one of the nin inputs (iw words each) or with another
+// of the nout outputs?
+static bool output_overlaps(u64 *const *out, int i, int nout, size_t ow, const u64 *const *in, int nin, size_t iw)
+{
+    for (int j = 0; j < nin; j++)
+        if (ranges_overlap(out[i], ow, in[j], iw)) return true;
+    for (int j = 0; j < nout; j++)
+        if (j != i && ranges_overlap(out[i], ow, out[j], ow)) return true;
+    return false;
+}
+
+static int check_galois_elt(mhe_ctx *c, u32 elt)
+{
+    if (!(elt & 1) || elt >= 2 * c->n) return fail(MHE_ERR_ARG, "Galois element is not valid");
+    return MHE_OK;
 }
 
 static void count_op(mhe_ctx *c, int kind, int L, unsigned long long k)
@@ -696,360 +707,8 @@ static int run_ntt_inv(mhe_ctx *c, const u64 *src, u64 *dst, int polys, int limb
     return MHE_OK;
 }
 
-// Key-switching inner product (evaluator.cpp:2410-2463): for output prime I (I == L -> P),
-// acc[k][I] = sum_J d_J[I] * key[J][k][I] mod q_I, where d_J[I] is the lifted NTT digit
-// (modup[I][J]) or, for I == J, the input target limb itself.  128-bit accumulation with a
-// single final Barrett reduction (digits are canonical so < 2^8 terms never overflow).
-__global__ __launch_bounds__(256) void k_ks_mac(const u64 *modup, const u64 *target, const u64 *key, u64 *acc,
-                                                const PrimeDev *primes, int L, int K, int key_limbs, int log_n, int I0)
-{
-    const u32 i = (blockIdx.x * 256 + threadIdx.x) * 2;
-    const int I = I0 + blockIdx.y;
-    const int pi = (I == L) ? K - 1 : I;
-    const int ki = (I == L) ? key_limbs - 1 : I;
-    const size_t n = (size_t)1 << log_n;
-    const PrimeDev p = primes[pi];
-    Acc128 a0x{ 0, 0 }, a0y{ 0, 0 }, a1x{ 0, 0 }, a1y{ 0, 0 };
-    const size_t kstride = (size_t)key_limbs * n;
-    for (int J = 0; J < L; J++)
-    {
-        const u64 *d = (I == J) ? target + (size_t)J * n : modup + ((size_t)(I - I0) * L + J) * n;
-        ulonglong2 x = *(const ulonglong2 *)(d + i);
-        const u64 *k0 = key + (size_t)(2 * J) * kstride + (size_t)ki * n;
-        ulonglong2 y0 = *(const ulonglong2 *)(k0 + i);
-        ulonglong2 y1 = *(const ulonglong2 *)(k0 + kstride + i);
-        mac128(a0x, x.x, y0.x);
-        mac128(a0y, x.y, y0.y);
-        mac128(a1x, x.x, y1.x);
-        mac128(a1y, x.y, y1.y);
-    }
-    ulonglong2 r0, r1;
-    r0.x = barrett128(a0x.lo, a0x.hi, p);
-    r0.y = barrett128(a0y.lo, a0y.hi, p);
-    r1.x = barrett128(a1x.lo, a1x.hi, p);
-    r1.y = barrett128(a1y.lo, a1y.hi, p);
-    *(ulonglong2 *)(acc + (size_t)I * n + i) = r0;
-    *(ulonglong2 *)(acc + (size_t)(L + 1 + I) * n + i) = r1;
-}
-
-// One entry of a (batched) key switch.
-struct KsJob
-{
-    u64 *ct;               // [2][L][n]
-    const u64 *target;     // [L][n], NTT form
-    const u64 *key;        // [digits][2][key_limbs][n]
-    int key_limbs;
-    u64 *rescale_out;      // HMult: [2][L-1][n] (see run_switch_key_batch), else nullptr
-};
-
-static int ks_check_key(mhe_ctx *c, const KsJob &j, int L, hipStream_t st, int *kpack)
-{
-    if (j.key_limbs < L + 1 || j.key_limbs > c->K) return fail(MHE_ERR_ARG, "kswitch_keys is not valid for encryption parameters");
-    // a prepared key (mhe_key_prepare) is recognised by the fused MAC itself (key_word_prepared
-    // on a word of each slot); the separate-MAC debugging path reads SEAL's layout only
-    *kpack = 1;
-    if (!c->ks_fused)
-    {
-        int tagged = 0;
-        int r0 = key_tagged(c, j.key, j.key_limbs, st, &tagged);
-        if (r0) return r0;
-        if (tagged) return fail(MHE_ERR_ARG, "key switch: prepared keys need the fused key MAC");
-        *kpack = 0;
-    }
-    // the key slice one switch streams: L digits x 2 polys x (L + 1) primes
-    c->key_bytes += 2ull * (unsigned long long)L * (unsigned long long)(L + 1) * c->n * 8ull;
-    // prepared: doubles stream the same 8 B per residue, the 48-bit planes 6 B for primes below 2^48
-    // (the format of a prepared key is not known here without a host sync: counted as doubles)
-    c->key_bytes_prep += 2ull * (unsigned long long)L * (unsigned long long)(L + 1) * c->n * 8ull;
-    return MHE_OK;
-}
-
-// Step 4 of a (batched) key switch, the ModDown (evaluator.cpp:2466-2524), over the key inner
-// products in w->e[e].acc (or accs[e]): ct_e += ModDown(acc_e), or with rescale_out the fused HMult tail (see
-// run_switch_key_batch).  special_inv_done: the key MAC already ran the special limbs' inverse
-// row pass.
-static void run_moddown(mhe_ctx *c, const KsJob *jobs, int B, int L, Workspace *w, int special_inv_done, int c1_write,
-                        hipStream_t st, u64 *const *accs = nullptr)
-{
-    // key products of entry e: accs[e] when given (hoisted rotations), else the entry's scratch
-    auto A = [&](int e) { return accs ? accs[e] : w->e[e].acc; };
-    const bool hm = jobs[0].rescale_out != nullptr;
-    const int log_n = c->log_n;
-    const size_t n = c->n;
-    // ModDown (evaluator.cpp:2466-2524): INTT_lazy of the special limbs, then fused
-    //    lift + NTT + (c + 4q - t) * P^-1 + add.
-    {
-        JobB<JobStrided> j;
-        j.per = 2;
-        for (int e = 0; e < B; e++) j.j[e] = special_limbs(c, A(e), L);
-        if (!special_inv_done) inv_row(j, log_n, 2 * B, c->nm, st);
-        // the special limbs' inverse column pass runs inside the lift column pass (k_icol_lift)
-        // (not in the HMult tail: JobMDRCol reads the fully inverse-transformed special limbs)
-        ColSrc cs{};
-        cs.stride = (size_t)(L + 1) * n;
-        cs.per = 2;
-        cs.primes = c->primes;
-        cs.itw = c->itw;
-        cs.pi = c->K - 1;
-        for (int e = 0; e < B; e++) cs.src[e] = A(e) + (size_t)L * n;
-        const bool fuse = c->icol_fused && (!hm || L < 2);
-        if (!fuse) inv_col(j, log_n, 2 * B, c->nm, st);
-        if (!hm || L < 2)
-        {
-            JobB<JobModDownCol> dc;
-            dc.per = 2 * L;
-            JobB<JobModDownRow> dr;
-            dr.per = 2 * L;
-            for (int e = 0; e < B; e++)
-            {
-                dc.j[e] = JobModDownCol{ A(e), w->e[e].modup, c->primes, c->tw, L, c->K, log_n };
-                dr.j[e] = JobModDownRow{ w->e[e].modup, A(e), jobs[e].ct, c->primes, c->tw, c->invq, L, c->K, log_n };
-                dr.j[e].fp = c->nm.fp ? 1 : 0;
-                dr.j[e].c1_write = c1_write;
-            }
-            if (fuse)
-                icol_lift(cs, dc, 2 * B, L, log_n, c->nm, st);
-            else
-                fwd_col(dc, log_n, 2 * L * B, c->nm, st);
-            fwd_row(dr, log_n, 2 * L * B, c->nm, st);
-        }
-        else
-        {
-            // ModDown of limb L-1 only, its INTT (the rescale's "last"), then ModDown and
-            // rescale of the other limbs through one forward NTT each
-            JobB<JobModDownCol> dc;
-            dc.per = 2;
-            JobB<JobModDownRow> dr;
-            dr.per = 2;
-            JobB<JobLastInv> li;
-            li.per = 2;
-            JobB<JobStrided> j2;
-            j2.per = 2;
-            JobB<JobMDRCol> mc;
-            mc.per = 2 * (L - 1);
-            JobB<JobMDRRow> mr;
-            mr.per = 2 * (L - 1);
-            for (int e = 0; e < B; e++)
-            {
-                dc.j[e] = JobModDownCol{ A(e), w->e[e].modup, c->primes, c->tw, L, c->K, log_n, L - 1 };
-                dr.j[e] = JobModDownRow{ w->e[e].modup, A(e), jobs[e].ct, c->primes, c->tw, c->invq, L, c->K, log_n, L - 1 };
-                dr.j[e].fp = c->nm.fp ? 1 : 0;
-                li.j[e] = JobLastInv{ jobs[e].ct, w->e[e].coeff, c->primes, c->itw, L, log_n, 1 };
-                j2.j[e] = JobStrided{ w->e[e].coeff, w->e[e].coeff, n, n, L - 1, 0, c->primes, c->itw, log_n, 1 };
-                mc.j[e] = JobMDRCol{ A(e), w->e[e].coeff, w->e[e].modup, c->primes, c->tw, c->invq, L, c->K, log_n,
-                                     c->nm.fp ? 1 : 0 };
-                mr.j[e] = JobMDRRow{ w->e[e].modup, A(e), jobs[e].ct, jobs[e].rescale_out, c->primes, c->tw, c->invq,
-                                     L, c->K, log_n, c->nm.fp ? 1 : 0 };
-            }
-            fwd_col(dc, log_n, 2 * B, c->nm, st);
-            fwd_row(dr, log_n, 2 * B, c->nm, st);
-            inv_row(li, log_n, 2 * B, c->nm, st);
-            inv_col(j2, log_n, 2 * B, c->nm, st);
-            if (c->nm.fp == 1)
-                col_lift2(mc, 2 * B, L - 1, log_n, c->nm, st);
-            else
-                fwd_col(mc, log_n, 2 * (L - 1) * B, c->nm, st);
-            fwd_row(mr, log_n, 2 * (L - 1) * B, c->nm, st);
-        }
-    }
-}
-
-// switch_key_inplace (evaluator.cpp:2281-2525) for B <= MHE_MAXB independent entries of one
-// level L, every kernel launched once for all of them: ct_e[2][L][n] += KS(target_e[L][n]).
-// rescale_out != nullptr (HMult; all entries or none): ct_e is the first two polys of a product,
-// and instead of ct += KS(target) the result of rescale_to_next(ct + KS(target)) goes to
-// rescale_out [2][L-1][n] (JobMDRCol / JobMDRRow); ct limb L-1 is overwritten on the way.
-// c1_write: ct[1] is taken as zero and written, not read (target may then alias ct[1]: it is last
-// read by the key MAC, before the ModDown writes ct).
-// front != nullptr (mhe_rotate_sum; fused key MAC only): stop before the ModDown, the key products
-// left in the entries' scratch (w->e[e].acc), ct untouched; *front = the key MAC already ran the
-// special limbs' inverse row pass.
-static int run_switch_key_batch(mhe_ctx *c, const KsJob *jobs, int B, int L, hipStream_t st, int c1_write = 0,
-                                int *front = nullptr)
-{
-    if (B < 1 || B > MHE_MAXB) return fail(MHE_ERR_ARG, "key switch: batch size out of range");
-    // mhe_debug_fail_switch's countdown (tests): this launch sequence fails before its first launch
-    for (int v = c->fail_switch.load(); v > 0;)
-        if (c->fail_switch.compare_exchange_weak(v, v - 1))
-        {
-            if (v == 1) return fail(MHE_ERR_MEMORY, "device allocation failed (injected)");
-            break;
-        }
-    const bool hm = jobs[0].rescale_out != nullptr;
-    for (int e = 0; e < B; e++)
-        if ((jobs[e].rescale_out != nullptr) != hm) return fail(MHE_ERR_ARG, "key switch: mixed fused-rescale batch");
-    if (c1_write && hm) return fail(MHE_ERR_ARG, "key switch: c1_write with a fused rescale");
-    if (!c->ks_fused && B > 1)
-    {
-        // the separate-MAC debugging path runs one entry at a time
-        for (int e = 0; e < B; e++)
-        {
-            int r = run_switch_key_batch(c, jobs + e, 1, L, st, c1_write);
-            if (r) return r;
-        }
-        return MHE_OK;
-    }
-    int kpack = 1;
-    for (int e = 0; e < B; e++)
-    {
-        int r = ks_check_key(c, jobs[e], L, st, &kpack);
-        if (r) return r;
-    }
-    count_op(c, MHE_OPK_KEYSWITCH, L, (unsigned long long)B);
-    if (hm) count_op(c, MHE_OPK_RESCALE, L, 2ull * B); // the fused HMult tail rescales both polys
-    Workspace *w;
-    int r = get_ws(c, st, c->K - 1, &w, B);
-    if (r) return r;
-    const int log_n = c->log_n;
-    const size_t n = c->n;
-    int special_inv_done = 0; // the fused MAC ran the special limbs' inverse row pass
-    // 1. t_target = INTT(target), canonical (evaluator.cpp:2351-2354)
-    {
-        JobB<JobStrided> j;
-        j.per = L;
-        for (int e = 0; e < B; e++) j.j[e] = JobStrided{ jobs[e].target, w->e[e].coeff, n, n, 0, 1, c->primes, c->itw, log_n, 0 };
-        inv_row(j, log_n, B * L, c->nm, st);
-        for (int e = 0; e < B; e++)
-        {
-            j.j[e].src = w->e[e].coeff;
-            j.j[e].mode = 1;
-        }
-        inv_col(j, log_n, B * L, c->nm, st);
-    }
-    if (c->ks_fused)
-    {
-        // 2+3. ModUp column pass, then its row pass fused with the key MAC so NTT'd digits
-        //      never leave registers (chunks of output primes sized for the Infinity Cache
-        //      measured slower at every size).
-        const int P = L + 1;
-        // 48-bit intermediate (ntt.h tile16): only k_modup_col writes it, so only with column groups
-        const int pack = (c->ks_pack && c->ks_colgroups > 0) ? 1 : 0;
-        KsPtrs kp{};
-        int share = B > 1 ? 1 : 0; // one key for every entry: XCD-grouped entries (k_ks_row_mac)
-        for (int e = 0; e < B; e++)
-            if (jobs[e].key != jobs[0].key || jobs[e].key_limbs != jobs[0].key_limbs) share = 0;
-        if (!c->ks_share) share = 0;
-        for (int e = 0; e < B; e++)
-        {
-            kp.coeff[e] = w->e[e].coeff;
-            kp.inter[e] = w->e[e].modup;
-            kp.target[e] = jobs[e].target;
-            kp.key[e] = jobs[e].key;
-            kp.acc[e] = w->e[e].acc;
-            kp.key_limbs[e] = jobs[e].key_limbs;
-        }
-        for (int I0 = 0; I0 <= L; I0 += P)
-        {
-            const int cnt = (I0 + P <= L + 1) ? P : L + 1 - I0;
-            hipEvent_t *tc = timing_slot(c, w, TK_MODUP_COL, st);
-            if (c->ks_colgroups > 0)
-            {
-                const int IG = c->ks_colgroups < cnt ? c->ks_colgroups : cnt;
-                modup_col(kp, B, c->primes, c->tw, L, c->K, log_n, c->nm_ks, I0, cnt, IG, pack, st);
-            }
-            else
-            {
-                JobB<JobModUpCol> j;
-                j.per = cnt * L;
-                for (int e = 0; e < B; e++) j.j[e] = JobModUpCol{ w->e[e].coeff, w->e[e].modup, c->primes, c->tw, L, c->K, log_n, I0 };
-                fwd_col(j, log_n, B * cnt * L, c->nm, st);
-            }
-            timing_end(tc, st);
-            hipEvent_t *tm = timing_slot(c, w, TK_KS_ROW_MAC, st);
-            const int has_special = (I0 <= L && L < I0 + cnt) ? 1 : 0;
-            special_inv_done |= ks_row_mac_chunk(kp, B, c->primes, c->tw, L, c->K, log_n, c->nm_ks, I0, cnt, pack, kpack,
-                                                 share, c->itw, has_special, st);
-            timing_end(tm, st);
-        }
-    }
-    else
-    {
-        // 2+3. (MHE_KS_FUSED=0, the independent debugging path) ModUp + key inner products in
-        //      three kernels: lift digit J to prime I and NTT it (evaluator.cpp:2386-2408; I == J
-        //      skipped), then acc[k][I] = sum_J digit * key[J][k][I] (evaluator.cpp:2410-2463).
-        //      (One entry: B == 1 here.)
-        const int P = L + 1;
-        for (int I0 = 0; I0 <= L; I0 += P)
-        {
-            const int cnt = (I0 + P <= L + 1) ? P : L + 1 - I0;
-            JobModUpCol j{ w->coeff, w->modup, c->primes, c->tw, L, c->K, log_n, I0 };
-            fwd_col(j, log_n, cnt * L, c->nm, st);
-            JobModUpRow r2{ w->modup, c->primes, c->tw, L, c->K, log_n, I0 };
-            fwd_row(r2, log_n, cnt * L, c->nm, st);
-            dim3 grid((unsigned)(n / 512), cnt);
-            hipLaunchKernelGGL(k_ks_mac, grid, dim3(256), 0, st, w->modup, jobs[0].target, jobs[0].key, w->acc, c->primes, L,
-                               c->K, jobs[0].key_limbs, log_n, I0);
-        }
-    }
-    if (front)
-        *front = special_inv_done;
-    else
-        run_moddown(c, jobs, B, L, w, special_inv_done, c1_write, st);
-    HIP_LAUNCH_CHECK();
-    return MHE_OK;
-}
-
-static int run_switch_key(mhe_ctx *c, u64 *ct, const u64 *target, const u64 *key, int key_limbs, int L,
-                          hipStream_t st, u64 *rescale_out = nullptr, int c1_write = 0)
-{
-    const KsJob j{ ct, target, key, key_limbs, rescale_out };
-    return run_switch_key_batch(c, &j, 1, L, st, c1_write);
-}
-
-// rescale_to_next (util/rns.cpp:737-808) of B <= MHE_MAXB independent ciphertexts of `size` polys
-// at L limbs, in[e] -> out[e] ([size][L-1][n]), every kernel launched once for all of them.
-static int run_rescale_batch(mhe_ctx *c, const u64 *const *in, u64 *const *out, int B, int size, int L, hipStream_t st)
-{
-    if (B < 1 || B > MHE_MAXB) return fail(MHE_ERR_ARG, "rescale: batch size out of range");
-    Workspace *w;
-    int r = get_ws(c, st, c->K - 1, &w, B);
-    if (r) return r;
-    count_op(c, MHE_OPK_RESCALE, L, (unsigned long long)B * size);
-    const int log_n = c->log_n;
-    // last[s] = INTT(in[s][L-1]) canonical -> the entry's coeff (size <= 3 polys)
-    JobB<JobLastInv> li;
-    li.per = size;
-    JobB<JobRescaleCol> rc;
-    rc.per = size * (L - 1);
-    JobB<JobRescaleRow> rr;
-    rr.per = size * (L - 1);
-    ColSrc cs{};
-    cs.stride = c->n;
-    cs.per = size;
-    cs.primes = c->primes;
-    cs.itw = c->itw;
-    cs.pi = L - 1;
-    for (int e = 0; e < B; e++)
-    {
-        li.j[e] = JobLastInv{ in[e], w->e[e].coeff, c->primes, c->itw, L, log_n, 1 };
-        rc.j[e] = JobRescaleCol{ w->e[e].coeff, w->e[e].modup, c->primes, c->tw, L, log_n };
-        rr.j[e] = JobRescaleRow{ w->e[e].modup, in[e], out[e], c->primes, c->tw, c->invq, L, c->K, log_n };
-        rr.j[e].fp = c->nm.fp ? 1 : 0;
-        cs.src[e] = w->e[e].coeff;
-    }
-    inv_row(li, log_n, size * B, c->nm, st);
-    if (c->icol_fused)
-    {
-        // the last limb's inverse column pass runs inside the lift column pass (k_icol_lift)
-        icol_lift(cs, rc, size * B, L - 1, log_n, c->nm, st);
-    }
-    else
-    {
-        JobB<JobStrided> j2;
-        j2.per = size;
-        for (int e = 0; e < B; e++) j2.j[e] = JobStrided{ w->e[e].coeff, w->e[e].coeff, c->n, c->n, L - 1, 0, c->primes, c->itw, log_n, 1 };
-        inv_col(j2, log_n, size * B, c->nm, st);
-        fwd_col(rc, log_n, size * (L - 1) * B, c->nm, st);
-    }
-    fwd_row(rr, log_n, size * (L - 1) * B, c->nm, st);
-    HIP_LAUNCH_CHECK();
-    return MHE_OK;
-}
-
-static int run_rescale(mhe_ctx *c, const u64 *in, u64 *out, int size, int L, hipStream_t st)
-{
-    return run_rescale_batch(c, &in, &out, 1, size, L, st);
-}
+// ------------------------------------------------------------- key switch and rescale pipelines
+#include "keyswitch.h"
 
 // ================================================================ internal (encode.hip)
 int mhe_internal_fail(int code, const char *msg)
@@ -1472,8 +1131,6 @@ MHE_EXPORT int mhe_ctx_set_timing(mhe_ctx *c, int on)
     return MHE_OK;
 }
 
-static bool hoist_ok(const mhe_ctx *c);
-
 MHE_EXPORT int mhe_trim(mhe_ctx *c)
 {
     if (!valid_ctx(c)) return fail(MHE_ERR_ARG, "context is not valid");
@@ -1501,32 +1158,6 @@ MHE_EXPORT int mhe_debug_fail_alloc(mhe_ctx *c, int nth)
 {
     if (!valid_ctx(c) || nth < 0) return fail(MHE_ERR_ARG, "invalid argument");
     c->fail_alloc.store(nth);
-    return MHE_OK;
-}
-
-MHE_EXPORT int mhe_ctx_set_hoist(mhe_ctx *c, int on, int check)
-{
-    if (!valid_ctx(c)) return fail(MHE_ERR_ARG, "context is not valid");
-    c->ks_hoist = on ? 1 : 0;
-    c->hoist_check = check ? 1 : 0;
-    return MHE_OK;
-}
-
-MHE_EXPORT int mhe_ctx_get_hoist(mhe_ctx *c, int *on, int *check)
-{
-    if (!valid_ctx(c) || !on || !check) return fail(MHE_ERR_ARG, "invalid argument");
-    *on = hoist_ok(c) ? 1 : 0;
-    *check = c->hoist_check.load();
-    return MHE_OK;
-}
-
-MHE_EXPORT int mhe_hoist_stats(mhe_ctx *c, uint64_t *rotations, uint64_t *mac_launches, uint64_t *check_mismatches,
-                               int reset)
-{
-    if (!valid_ctx(c) || !rotations || !mac_launches || !check_mismatches) return fail(MHE_ERR_ARG, "invalid argument");
-    *rotations = reset ? c->hoist_rot.exchange(0) : c->hoist_rot.load();
-    *mac_launches = reset ? c->hoist_mac.exchange(0) : c->hoist_mac.load();
-    *check_mismatches = reset ? c->hoist_bad.exchange(0) : c->hoist_bad.load();
     return MHE_OK;
 }
 
@@ -1990,7 +1621,8 @@ MHE_EXPORT int mhe_relinearize(mhe_ctx *c, uint64_t *ct3, const uint64_t *key, i
 
 static int launch_galois(mhe_ctx *c, const u64 *in, u32 elt, u64 *out, int polys, int limbs, hipStream_t st)
 {
-    if (!(elt & 1) || elt >= 2 * c->n) return fail(MHE_ERR_ARG, "Galois element is not valid");
+    int r = check_galois_elt(c, elt);
+    if (r) return r;
     count_op(c, MHE_OPK_GALOIS, limbs, (unsigned long long)polys);
     size_t total = (size_t)polys * limbs << c->log_n;
     hipLaunchKernelGGL(k_galois, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, in, out, elt, c->log_n,
@@ -2063,764 +1695,8 @@ MHE_EXPORT int mhe_apply_galois_to(mhe_ctx *c, const uint64_t *in, uint64_t *out
     return run_switch_key(c, out, w->tmp, key, key_limbs, limbs, st);
 }
 
-// ------------------------------------------------------------------ hoisted rotations (hoist.h)
-// The ModUp buffers of up to `entries` hoisted inputs on stream st ([K][K-1][n] each: every level),
-// the key products of up to MHE_MAXB * MHE_HOIST_R of their rotations and the inputs' flags.
-static int get_hoist(mhe_ctx *c, hipStream_t st, int entries, int ws_entries, int L, Workspace **out)
-{
-    Workspace *w;
-    int r = get_ws(c, st, c->K - 1, &w, std::max(entries, ws_entries));
-    if (r) return r;
-    std::lock_guard<std::mutex> g(w->mu);
-    // per input [L+1][L][n] (the pass's level), the key products of up to MHE_MAXB * MHE_HOIST_R
-    // rotations at that level; grown (after draining the stream) when a pass needs more
-    if (w->hoist_entries < entries || w->hoist_limbs < L)
-    {
-        const int E = std::max(entries, w->hoist_entries), HL = std::max(L, w->hoist_limbs);
-        w->hoist_entries = 0;
-        w->hoist_limbs = 0;
-        const size_t per = (size_t)(HL + 1) * HL * c->n, pacc = (size_t)2 * (HL + 1) * c->n;
-        const int na = MHE_MAXB * MHE_HOIST_R;
-        if ((r = w->hoist_base.grow(c, st, ((size_t)E * per + (size_t)na * pacc) * sizeof(u64)))) return r;
-        for (int i = 0; i < E; i++) w->hoist[i] = w->hoist_base.p + (size_t)i * per;
-        for (int i = 0; i < na; i++) w->hacc[i] = w->hoist_base.p + (size_t)E * per + (size_t)i * pacc;
-        w->hoist_entries = E;
-        w->hoist_limbs = HL;
-    }
-    if (!w->flags && hipMalloc(&w->flags, MHE_MAXB * sizeof(int)) != hipSuccess)
-        return fail(MHE_ERR_MEMORY, "workspace allocation failed");
-    *out = w;
-    return MHE_OK;
-}
-
-// M^g = NTT of Galois element g's negation mask under every prime of the context, [K][n]
-// canonical; built once per element on stream st (which then waits for it: other streams use the
-// table without an event).
-static int get_mask(mhe_ctx *c, u32 elt, hipStream_t st, const u64 **out)
-{
-    std::lock_guard<std::mutex> g(c->mask_mu);
-    auto it = c->masks.find(elt);
-    if (it != c->masks.end())
-    {
-        *out = it->second;
-        return MHE_OK;
-    }
-    u64 *m = nullptr;
-    const size_t total = (size_t)c->K * c->n;
-    HIP_TRY(hipSetDevice(c->device));
-    if (hipMalloc(&m, total * sizeof(u64)) != hipSuccess) return fail(MHE_ERR_MEMORY, "Galois mask allocation failed");
-    hipLaunchKernelGGL(k_negmask, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, m, elt, c->K, c->log_n);
-    fwd_col(fwd_plain(c, m, m, c->K, 0), c->log_n, c->K, c->nm, st);
-    fwd_row(fwd_plain(c, m, m, c->K, 1), c->log_n, c->K, c->nm, st);
-    HIP_LAUNCH_CHECK();
-    HIP_TRY(hipStreamSynchronize(st));
-    c->masks[elt] = m;
-    *out = m;
-    return MHE_OK;
-}
-
-static void launch_hoist_mac(int R, dim3 grid, hipStream_t st, const HoistPtrs &hp, const PrimeDev *primes,
-                             const TwF *cm, int L, int K, int log_n)
-{
-    switch (R)
-    {
-#define HM(r) case r: hipLaunchKernelGGL((k_ks_hoist_mac<r>), grid, dim3(256), 0, st, hp, primes, cm, L, K, log_n); break;
-        HM(1) HM(2) HM(3) HM(4) HM(5) HM(6) HM(7) HM(8)
-#undef HM
-    }
-}
-static void launch_hoist_mac_sh(int R, dim3 grid, hipStream_t st, const HoistShared &hs, const PrimeDev *primes,
-                                const TwF *cm, int L, int K, int log_n)
-{
-    switch (R)
-    {
-#define HM(r) case r: hipLaunchKernelGGL((k_ks_hoist_mac_sh<r>), grid, dim3(1024), 0, st, hs, primes, cm, L, K, log_n); break;
-        HM(1) HM(2) HM(3) HM(4) HM(5) HM(6) HM(7) HM(8)
-#undef HM
-    }
-}
-
-static bool hoist_ok(const mhe_ctx *c)
-{
-    return c->ks_hoist && c->ks_fused && c->galois_fused && c->ks_colgroups > 0 && c->nm.fp == 1 && c->nm_ks.fp == 1 &&
-           c->cmodf;
-}
-
-// counts words that differ between a and b (mhe_ctx_set_hoist's check); first[0] = lowest index
-__global__ void k_cmp_words(const u64 *__restrict__ a, const u64 *__restrict__ b, size_t total,
-                            unsigned long long *bad)
-{
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total || a[i] == b[i]) return;
-    atomicAdd(bad, 1ull);
-    atomicMin(bad + 1, (unsigned long long)i);
-}
-
-// The check of a hoisted pass: every rotation again by SEAL's order (permutation, then the classic
-// key switch of the permuted c1) into scratch, compared word for word with the hoisted output.
-static int hoist_check_pass(mhe_ctx *c, const u64 *const *in, int count, const int *ent_in, u64 *const *out,
-                            const u32 *elts, const u64 *const *keys, const int *key_limbs, int L, hipStream_t st,
-                            const int *flags)
-{
-    const size_t ps = (size_t)L * c->n;
-    u64 *tmp = nullptr;
-    unsigned long long *cnt = nullptr;
-    HIP_TRY(hipSetDevice(c->device));
-    if (hipMalloc(&tmp, (size_t)MHE_MAXB * 2 * ps * sizeof(u64)) != hipSuccess)
-        return fail(MHE_ERR_MEMORY, "hoist check: allocation failed");
-    if (hipMalloc(&cnt, 2 * MHE_MAXB * sizeof(unsigned long long) + MHE_MAXB * sizeof(int)) != hipSuccess)
-    {
-        (void)hipFree(tmp);
-        return fail(MHE_ERR_MEMORY, "hoist check: allocation failed");
-    }
-    int *fl = reinterpret_cast<int *>(cnt + 2 * MHE_MAXB);
-    int r = MHE_OK;
-    for (int i0 = 0; i0 < count && r == MHE_OK; i0 += MHE_MAXB)
-    {
-        const int B = std::min(MHE_MAXB, count - i0);
-        GalPtrs gp{};
-        KsJob jobs[MHE_MAXB];
-        std::vector<unsigned long long> init(2 * MHE_MAXB);
-        for (int e = 0; e < B; e++)
-        {
-            const int i = i0 + e;
-            u64 *t = tmp + (size_t)e * 2 * ps;
-            gp.in[e] = in[ent_in[i]];
-            gp.out[e] = t;
-            gp.elt[e] = elts[i];
-            jobs[e] = KsJob{ t, t + ps, keys[i], key_limbs[i], nullptr };
-            init[2 * e] = 0;
-            init[2 * e + 1] = ~0ull;
-        }
-        HIP_TRY(hipMemcpyAsync(cnt, init.data(), init.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
-        for (int e = 0; e < B; e++)
-            HIP_TRY(hipMemcpyAsync(fl + e, flags + ent_in[i0 + e], sizeof(int), hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(k_galois_b, dim3((unsigned)((2 * ps + 255) / 256), (unsigned)B), dim3(256), 0, st, gp,
-                           c->log_n, 2 * ps);
-        HIP_LAUNCH_CHECK();
-        if ((r = run_switch_key_batch(c, jobs, B, L, st, 1))) break;
-        for (int e = 0; e < B; e++)
-            hipLaunchKernelGGL(k_cmp_words, dim3((unsigned)((2 * ps + 255) / 256)), dim3(256), 0, st,
-                               tmp + (size_t)e * 2 * ps, out[i0 + e], 2 * ps, cnt + 2 * e);
-        HIP_LAUNCH_CHECK();
-        std::vector<unsigned long long> got(2 * MHE_MAXB);
-        std::vector<int> hf(MHE_MAXB);
-        HIP_TRY(hipMemcpyAsync(got.data(), cnt, got.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(hf.data(), fl, MHE_MAXB * sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        for (int e = 0; e < B; e++)
-        {
-            if (!got[2 * e]) continue;
-            c->hoist_bad += got[2 * e];
-            const unsigned long long f = got[2 * e + 1];
-            fprintf(stderr,
-                    "[hoist check] stream %p L %d entry %d/%d (input %d, elt %u, key %p, key_limbs %d, zero flag %d): "
-                    "%llu words differ, first at poly %llu limb %llu slot %llu\n",
-                    (void *)st, L, i0 + e, count, ent_in[i0 + e], elts[i0 + e], (const void *)keys[i0 + e],
-                    key_limbs[i0 + e], hf[e], got[2 * e], f / ps, (f % ps) / c->n, f % c->n);
-        }
-    }
-    (void)hipStreamSynchronize(st);
-    (void)hipFree(tmp);
-    (void)hipFree(cnt);
-    return r;
-}
-
-// Rotations of H <= MHE_MAXB inputs at L limbs, entry i rotating input ent_in[i] (index into in)
-// by elts[i] into out[i]: ModUp of every input once (INTT -> column pass -> row pass, canonical
-// D in the hoist buffers, plus the zero scan), then per chunk of entries the permutation of c0 /
-// c1 into out, the hoisted key MAC (hoist.h), the classic ModUp + MAC for flagged inputs only
-// (their kernels return at once otherwise), and the ModDown (c1 written).
-static int run_galois_hoisted(mhe_ctx *c, const u64 *const *in, int H, int count, const int *ent_in,
-                              u64 *const *out, const u32 *elts, const u64 *const *keys, const int *key_limbs, int L,
-                              hipStream_t st)
-{
-    Workspace *w;
-    int r = get_hoist(c, st, H, std::min(count, MHE_MAXB), L, &w); // step 3 uses up to MHE_MAXB entry slots
-    if (r) return r;
-    const int log_n = c->log_n;
-    const size_t n = c->n, ps = (size_t)L * n;
-    std::vector<const u64 *> masks(count);
-    std::vector<u32> elt_inv(count);
-    for (int i = 0; i < count; i++)
-    {
-        if ((r = get_mask(c, elts[i], st, &masks[i]))) return r;
-        u64 inv = 0;
-        host::invmod(elts[i], 2 * n, inv); // odd: a unit mod 2N
-        elt_inv[i] = (u32)inv;
-    }
-    // 1. ModUp of each input's c1: INTT (evaluator.cpp:2351-2354) into entry slot h's coeff, the zero
-    //    scan, the column pass into hoist[h] (64-bit, natural order), the row pass in place
-    {
-        JobB<JobStrided> j;
-        j.per = L;
-        for (int h = 0; h < H; h++)
-            j.j[h] = JobStrided{ in[h] + ps, w->e[h].coeff, n, n, 0, 1, c->primes, c->itw, log_n, 0 };
-        inv_row(j, log_n, H * L, c->nm, st);
-        for (int h = 0; h < H; h++)
-        {
-            j.j[h].src = w->e[h].coeff;
-            j.j[h].mode = 1;
-        }
-        inv_col(j, log_n, H * L, c->nm, st);
-        HIP_TRY(hipMemsetAsync(w->flags, 0, MHE_MAXB * sizeof(int), st));
-        for (int h = 0; h < H; h++)
-            hipLaunchKernelGGL(k_zero_scan, dim3((unsigned)((ps + 255) / 256)), dim3(256), 0, st, w->e[h].coeff, log_n, ps,
-                               w->flags + h);
-        KsPtrs kp{};
-        for (int h = 0; h < H; h++)
-        {
-            kp.coeff[h] = w->e[h].coeff;
-            kp.inter[h] = w->e[h].modup;
-        }
-        const int IG = c->ks_colgroups < L + 1 ? c->ks_colgroups : L + 1;
-        modup_col(kp, H, c->primes, c->tw, L, c->K, log_n, c->nm_ks, 0, L + 1, IG, 0, st);
-        auto row = [&](auto brev) {
-            JobB<JobModUpRowH<decltype(brev)::value>> rj;
-            rj.per = (L + 1) * L;
-            for (int h = 0; h < H; h++) rj.j[h] = { w->e[h].modup, w->hoist[h], c->primes, c->tw, L, c->K, log_n };
-            fwd_row(rj, log_n, H * (L + 1) * L, c->nm, st);
-        };
-        if (log_n == 16)
-            row(std::true_type{});
-        else
-            row(std::false_type{});
-        HIP_LAUNCH_CHECK();
-    }
-    // 2. the hoisted key MAC: items of one input and up to MHE_HOIST_R of its rotations (sorted by
-    //    key, so the items of images rotated alike list the same keys and share their rows), up to
-    //    MHE_MAXB items per launch; rotation i's key products go to w->hacc[i]
-    const int pack = (c->ks_pack && c->ks_colgroups > 0) ? 1 : 0;
-    {
-        std::vector<std::vector<int>> per(H);
-        for (int i = 0; i < count; i++) per[ent_in[i]].push_back(i);
-        std::vector<std::pair<int, std::vector<int>>> items;
-        for (int h = 0; h < H; h++)
-        {
-            std::stable_sort(per[h].begin(), per[h].end(), [&](int a, int b) { return keys[a] < keys[b]; });
-            for (size_t r0 = 0; r0 < per[h].size(); r0 += MHE_HOIST_R)
-                items.emplace_back(h, std::vector<int>(per[h].begin() + r0,
-                                                       per[h].begin() + std::min(per[h].size(), r0 + MHE_HOIST_R)));
-        }
-        // items with one key list (the images of a FiberBatch rotated alike): the shared-key kernel,
-        // up to MHE_MAXB items per launch; the rest one launch per up to MHE_MAXB items
-        std::vector<char> done(items.size(), 0);
-        for (size_t z0 = 0; z0 < items.size(); z0++)
-        {
-            if (done[z0]) continue;
-            std::vector<size_t> same{ z0 };
-            for (size_t z = z0 + 1; z < items.size() && same.size() < (size_t)MHE_MAXB; z++)
-            {
-                if (done[z] || items[z].second.size() != items[z0].second.size()) continue;
-                bool eq = true;
-                for (size_t r = 0; eq && r < items[z].second.size(); r++)
-                {
-                    const int a = items[z].second[r], b = items[z0].second[r];
-                    eq = keys[a] == keys[b] && key_limbs[a] == key_limbs[b] && elts[a] == elts[b];
-                }
-                if (eq) same.push_back(z);
-            }
-            if (same.size() < 2) continue;
-            HoistShared hs{};
-            hs.Z = (int)same.size();
-            const std::vector<int> &r0 = items[z0].second;
-            for (size_t r = 0; r < r0.size(); r++)
-            {
-                hs.key[r] = keys[r0[r]];
-                hs.mask[r] = masks[r0[r]];
-                hs.einv[r] = elt_inv[r0[r]];
-                hs.key_limbs[r] = key_limbs[r0[r]];
-            }
-            for (int z = 0; z < hs.Z; z++)
-            {
-                const auto &it = items[same[z]];
-                hs.D[z] = w->hoist[it.first];
-                hs.c1[z] = in[it.first] + ps;
-                hs.flag[z] = w->flags + it.first;
-                for (size_t r = 0; r < it.second.size(); r++) hs.acc[z][r] = w->hacc[it.second[r]];
-                done[same[z]] = 1;
-            }
-            hipEvent_t *tm = timing_slot(c, w, TK_KS_ROW_MAC, st);
-            const int per_wg = r0.size() <= 4 ? 8 : 4; // 4 lane groups x items per lane
-            launch_hoist_mac_sh((int)r0.size(), dim3((unsigned)(n / 256), (unsigned)(L + 1), (unsigned)((hs.Z + per_wg - 1) / per_wg)),
-                                st, hs, c->primes, c->cmodf, L, c->K, log_n);
-            c->hoist_mac++;
-            timing_end(tm, st);
-        }
-        std::vector<std::pair<int, std::vector<int>>> left;
-        for (size_t z = 0; z < items.size(); z++)
-            if (!done[z]) left.push_back(items[z]);
-        items.swap(left);
-        // one rotation count per launch (k_ks_hoist_mac<R>): items ordered by it
-        std::stable_sort(items.begin(), items.end(),
-                         [](const std::pair<int, std::vector<int>> &a, const std::pair<int, std::vector<int>> &b) {
-                             return a.second.size() > b.second.size();
-                         });
-        for (size_t z0 = 0; z0 < items.size();)
-        {
-            size_t zn = z0 + 1;
-            while (zn < items.size() && zn - z0 < (size_t)MHE_MAXB && items[zn].second.size() == items[z0].second.size()) zn++;
-            const int Z = (int)(zn - z0);
-            HoistPtrs hp{};
-            for (int z = 0; z < Z; z++)
-            {
-                const int h = items[z0 + z].first;
-                const std::vector<int> &rs = items[z0 + z].second;
-                hp.D[z] = w->hoist[h];
-                hp.c1[z] = in[h] + ps;
-                hp.flag[z] = w->flags + h;
-                hp.R[z] = (int)rs.size();
-                for (size_t r = 0; r < rs.size(); r++)
-                {
-                    const int i = rs[r];
-                    hp.key[z][r] = keys[i];
-                    hp.mask[z][r] = masks[i];
-                    hp.acc[z][r] = w->hacc[i];
-                    hp.einv[z][r] = elt_inv[i];
-                    hp.key_limbs[z][r] = key_limbs[i];
-                }
-            }
-            const dim3 grid((unsigned)(n / 256), (unsigned)(L + 1), (unsigned)Z);
-            hipEvent_t *tm = timing_slot(c, w, TK_KS_ROW_MAC, st);
-            launch_hoist_mac(hp.R[0], grid, st, hp, c->primes, c->cmodf, L, c->K, log_n);
-            c->hoist_mac++;
-            timing_end(tm, st);
-            z0 = zn;
-        }
-        HIP_LAUNCH_CHECK();
-    }
-    // 3. per MHE_MAXB rotations: c0 / c1 permuted into out, the classic ModUp + MAC of flagged
-    //    inputs (their kernels return at once otherwise), the ModDown (c1 written)
-    std::vector<int> order(count);
-    for (int i = 0; i < count; i++) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return keys[a] < keys[b]; });
-    for (int i0 = 0; i0 < count; i0 += MHE_MAXB)
-    {
-        const int B = std::min(MHE_MAXB, count - i0);
-        GalPtrs gp{};
-        KsPtrs kp{};
-        KsJob jobs[MHE_MAXB];
-        u64 *accs[MHE_MAXB];
-        JobB<JobStrided> ij;
-        ij.per = L;
-        int share = B > 1 ? 1 : 0;
-        for (int e = 0; e < B; e++)
-        {
-            const int i = order[i0 + e], h = ent_in[i];
-            gp.in[e] = in[h];
-            gp.out[e] = out[i];
-            gp.elt[e] = elts[i];
-            jobs[e] = KsJob{ out[i], out[i] + ps, keys[i], key_limbs[i], nullptr };
-            accs[e] = w->hacc[i];
-            // the classic path of a flagged input: INTT of the permuted c1, ModUp, fused MAC
-            ij.j[e] = JobStrided{ out[i] + ps, w->e[e].coeff, n, n, 0, 1, c->primes, c->itw, log_n, 0, w->flags + h };
-            kp.coeff[e] = w->e[e].coeff;
-            kp.inter[e] = w->e[e].modup;
-            kp.target[e] = out[i] + ps;
-            kp.key[e] = keys[i];
-            kp.acc[e] = w->hacc[i];
-            kp.key_limbs[e] = key_limbs[i];
-            kp.run_if[e] = w->flags + h;
-            if (keys[i] != keys[order[i0]] || key_limbs[i] != key_limbs[order[i0]]) share = 0;
-        }
-        if (!c->ks_share) share = 0;
-        int kpack = 1;
-        for (int e = 0; e < B; e++)
-            if ((r = ks_check_key(c, jobs[e], L, st, &kpack))) return r;
-        count_op(c, MHE_OPK_GALOIS, L, 2ull * B);
-        count_op(c, MHE_OPK_KEYSWITCH, L, (unsigned long long)B);
-        const size_t total = 2 * ps;
-        hipLaunchKernelGGL(k_galois_b, dim3((unsigned)((total + 255) / 256), (unsigned)B), dim3(256), 0, st, gp, log_n,
-                           total);
-        inv_row(ij, log_n, B * L, c->nm, st);
-        for (int e = 0; e < B; e++)
-        {
-            ij.j[e].src = w->e[e].coeff;
-            ij.j[e].mode = 1;
-        }
-        inv_col(ij, log_n, B * L, c->nm, st);
-        const int IG = c->ks_colgroups < L + 1 ? c->ks_colgroups : L + 1;
-        modup_col(kp, B, c->primes, c->tw, L, c->K, log_n, c->nm_ks, 0, L + 1, IG, pack, st);
-        ks_row_mac_chunk(kp, B, c->primes, c->tw, L, c->K, log_n, c->nm_ks, 0, L + 1, pack, kpack, share, c->itw, 0, st);
-        HIP_LAUNCH_CHECK();
-        run_moddown(c, jobs, B, L, w, 0, 1, st, accs);
-    }
-    c->hoist_rot += (unsigned long long)count;
-    if (c->hoist_check) return hoist_check_pass(c, in, count, ent_in, out, elts, keys, key_limbs, L, st, w->flags);
-    return MHE_OK;
-}
-
-MHE_EXPORT int mhe_apply_galois_batch(mhe_ctx *c, int count, const uint64_t *const *in, uint64_t *const *out,
-                                      const uint32_t *elts, const uint64_t *const *keys, const int *key_limbs, int limbs,
-                                      void *s)
-{
-    int r = check_limbs(c, limbs, 1);
-    if (r) return r;
-    if (count < 0 || (count && (!in || !out || !elts || !keys || !key_limbs))) return fail(MHE_ERR_ARG, "invalid argument");
-    hipStream_t st = S(s);
-    const size_t ps = (size_t)limbs << c->log_n;
-    for (int i = 0; i < count; i++)
-    {
-        if (!in[i] || !out[i] || !keys[i]) return fail(MHE_ERR_ARG, "Galois key not present");
-        if (!(elts[i] & 1) || elts[i] >= 2 * c->n) return fail(MHE_ERR_ARG, "Galois element is not valid");
-        // every key is checked before the first launch, so a bad key leaves no output half-written
-        if (key_limbs[i] < limbs + 1 || key_limbs[i] > c->K)
-            return fail(MHE_ERR_ARG, "kswitch_keys is not valid for encryption parameters");
-        // outputs must be disjoint from every input and from each other (all are written before the
-        // first key switch reads its input's permutation back from its own output)
-        for (int j = 0; j < count; j++)
-        {
-            const bool ov_in = ranges_overlap(out[i], 2 * ps, in[j], 2 * ps);
-            const bool ov_out = j != i && ranges_overlap(out[i], 2 * ps, out[j], 2 * ps);
-            if (ov_in || ov_out) return fail(MHE_ERR_ARG, "result cannot point to the same value as operand");
-        }
-    }
-    if (!c->galois_fused)
-    {
-        for (int i = 0; i < count; i++)
-            if ((r = mhe_apply_galois_to(c, in[i], out[i], elts[i], keys[i], key_limbs[i], limbs, s))) return r;
-        return MHE_OK;
-    }
-    // inputs rotated more than once share their ModUp (hoist.h), up to MHE_MAXB inputs per pass
-    std::vector<int> rest;
-    if (hoist_ok(c) && count > 1 && c->n >= 256)
-    {
-        std::vector<const u64 *> uin;
-        std::vector<std::vector<int>> uent;
-        for (int i = 0; i < count; i++)
-        {
-            size_t u = 0;
-            while (u < uin.size() && uin[u] != in[i]) u++;
-            if (u == uin.size())
-            {
-                uin.push_back(in[i]);
-                uent.emplace_back();
-            }
-            uent[u].push_back(i);
-        }
-        std::vector<const u64 *> hin;
-        std::vector<int> ent_in;
-        std::vector<u64 *> hout;
-        std::vector<u32> hel;
-        std::vector<const u64 *> hkey;
-        std::vector<int> hkl;
-        auto flush = [&]() -> int {
-            if (hin.empty()) return MHE_OK;
-            const int rr = run_galois_hoisted(c, hin.data(), (int)hin.size(), (int)ent_in.size(), ent_in.data(), hout.data(),
-                                              hel.data(), hkey.data(), hkl.data(), limbs, st);
-            hin.clear();
-            ent_in.clear();
-            hout.clear();
-            hel.clear();
-            hkey.clear();
-            hkl.clear();
-            return rr;
-        };
-        for (size_t u = 0; u < uin.size(); u++)
-        {
-            if (uent[u].size() < 2)
-            {
-                rest.push_back(uent[u][0]);
-                continue;
-            }
-            // at most MHE_MAXB inputs and MHE_MAXB * MHE_HOIST_R rotations per pass (w->hacc)
-            if ((hin.size() == MHE_MAXB || ent_in.size() + uent[u].size() > (size_t)MHE_MAXB * MHE_HOIST_R) &&
-                (r = flush()))
-                return r;
-            if (uent[u].size() > (size_t)MHE_MAXB * MHE_HOIST_R)
-            {
-                // more rotations than one pass holds: the classic path (never in the callers' shapes)
-                for (int i : uent[u]) rest.push_back(i);
-                continue;
-            }
-            const int h = (int)hin.size();
-            hin.push_back(uin[u]);
-            for (int i : uent[u])
-            {
-                ent_in.push_back(h);
-                hout.push_back(out[i]);
-                hel.push_back(elts[i]);
-                hkey.push_back(keys[i]);
-                hkl.push_back(key_limbs[i]);
-            }
-        }
-        if ((r = flush())) return r;
-    }
-    else
-        for (int i = 0; i < count; i++) rest.push_back(i);
-    // entries of one key side by side: a launch of them shares the key stream (k_ks_row_mac share)
-    std::stable_sort(rest.begin(), rest.end(), [&](int a, int b) { return keys[a] < keys[b]; });
-    const int nrest = (int)rest.size();
-    for (int i0 = 0; i0 < nrest; i0 += MHE_MAXB)
-    {
-        const int B = std::min(MHE_MAXB, nrest - i0);
-        // out_e <- perm_e(in_e), both polys, one launch (evaluator.cpp:2193-2214; SEAL zeroes c1 and
-        // adds KS_1, the same words as writing it)
-        GalPtrs gp{};
-        KsJob jobs[MHE_MAXB];
-        for (int e = 0; e < B; e++)
-        {
-            const int i = rest[i0 + e];
-            gp.in[e] = in[i];
-            gp.out[e] = out[i];
-            gp.elt[e] = elts[i];
-            jobs[e] = KsJob{ out[i], out[i] + ps, keys[i], key_limbs[i], nullptr };
-        }
-        const size_t total = 2 * ps;
-        count_op(c, MHE_OPK_GALOIS, limbs, 2ull * B);
-        hipLaunchKernelGGL(k_galois_b, dim3((unsigned)((total + 255) / 256), (unsigned)B), dim3(256), 0, st, gp, c->log_n,
-                           total);
-        HIP_LAUNCH_CHECK();
-        if ((r = run_switch_key_batch(c, jobs, B, limbs, st, 1))) return r;
-    }
-    return MHE_OK;
-}
-
-// ------------------------------------------------------------------------------ rotate and sum
-// mhe_rotate_sum: the key products of a chunk's entries folded into their groups' accumulators,
-// before the one ModDown forward NTT per limb of each group.  A chunk's entries come sorted by key
-// (they share the key stream of the MAC), so a group's entries are anywhere in it: zof[e] is the
-// chunk's group of entry e.  Every special limb has been through its own inverse NTT ([0, 2P)), so
-// each lift is SEAL's integer (evaluator.cpp:2466-2524) and the sums that follow are sums of
-// canonical residues mod q_i: the special limbs are never added mod P.
-struct RotSumPtrs
-{
-    const u64 *acc[MHE_MAXB];  // entry: key products [2][L+1][n], special limbs in coefficient form
-    const u64 *perm[MHE_MAXB]; // entry: permuted c0 [L][n]
-    u64 *A[MHE_MAXB];          // group: sum of the key products [2][L+1][n] (limbs 0 .. L-1 used)
-    u64 *T[MHE_MAXB];          // group: sum of the lifted special limbs [2][L][n], coefficient form
-    u64 *out[MHE_MAXB];        // group: out[0] += (or =) the permuted c0s
-    int zof[MHE_MAXB];         // entry: its group among the chunk's
-    int B;                     // entries in the chunk
-    int first[MHE_MAXB];       // group: its first chunk (A and T written, not added to)
-    int write0[MHE_MAXB];      // group: out[0] written, not added to (first chunk without accumulate)
-};
-
-// grid (n / 512, 2 * L, groups in the chunk); one lane owns two adjacent words of (group, k, i)
-__global__ __launch_bounds__(256) void k_rotsum_acc(RotSumPtrs P, const PrimeDev *__restrict__ primes, int L, int K,
-                                                    int log_n)
-{
-    const int z = blockIdx.z, k = blockIdx.y / L, i = blockIdx.y - k * L;
-    const size_t x = ((size_t)blockIdx.x * 256 + threadIdx.x) * 2;
-    const size_t n = (size_t)1 << log_n;
-    JobModDownCol::View v; // the ModDown column pass's lift, with its constants
-    v.p = prime_at(primes, i);
-    v.P = prime_at(primes, K - 1);
-    v.half = v.P.q >> 1;
-    v.fix = v.p.q - barrett64(v.half, v.p);
-    v.reduce = v.P.q > v.p.q;
-    const u64 q = v.p.q;
-    const size_t oa = (size_t)(k * (L + 1) + i) * n + x, os = (size_t)(k * (L + 1) + L) * n + x;
-    const size_t ot = (size_t)(k * L + i) * n + x, oc = (size_t)i * n + x;
-    ulonglong2 a{ 0, 0 }, t{ 0, 0 }, c0{ 0, 0 };
-    if (!P.first[z])
-    {
-        a = *(const ulonglong2 *)(P.A[z] + oa);
-        t = *(const ulonglong2 *)(P.T[z] + ot);
-    }
-    if (k == 0 && !P.write0[z]) c0 = *(const ulonglong2 *)(P.out[z] + oc);
-    for (int e = 0; e < P.B; e++)
-    {
-        if (P.zof[e] != z) continue; // uniform over the workgroup
-        const ulonglong2 ae = *(const ulonglong2 *)(P.acc[e] + oa);
-        const ulonglong2 se = *(const ulonglong2 *)(P.acc[e] + os);
-        a.x = addmod(a.x, ae.x, q);
-        a.y = addmod(a.y, ae.y, q);
-        t.x = addmod(t.x, csub(v.lift(se.x), q), q); // lift() is in [0, 2q)
-        t.y = addmod(t.y, csub(v.lift(se.y), q), q);
-        if (k == 0)
-        {
-            const ulonglong2 ce = *(const ulonglong2 *)(P.perm[e] + oc);
-            c0.x = addmod(c0.x, ce.x, q);
-            c0.y = addmod(c0.y, ce.y, q);
-        }
-    }
-    *(ulonglong2 *)(P.A[z] + oa) = a;
-    *(ulonglong2 *)(P.T[z] + ot) = t;
-    if (k == 0) *(ulonglong2 *)(P.out[z] + oc) = c0;
-}
-
-// The scratch of mhe_rotate_sum on stream st: the workspace for `entries` batch entries and the
-// accumulators of MHE_MAXB groups at L limbs (grown, after draining the stream, when a call needs a
-// higher level).
-static int get_rotsum(mhe_ctx *c, hipStream_t st, int entries, int L, Workspace **out)
-{
-    Workspace *w;
-    int r = get_ws(c, st, c->K - 1, &w, entries);
-    if (r) return r;
-    std::lock_guard<std::mutex> g(w->mu);
-    if (w->rs_limbs < L)
-    {
-        w->rs_limbs = 0;
-        if ((r = w->rs_base.grow(c, st, (size_t)MHE_MAXB * (4 * (size_t)L + 2) * c->n * sizeof(u64)))) return r;
-        w->rs_limbs = L;
-    }
-    *out = w;
-    return MHE_OK;
-}
-
-MHE_EXPORT int mhe_rotsum_stats(mhe_ctx *c, uint64_t *sums, uint64_t *terms, int reset)
-{
-    if (!valid_ctx(c) || !sums || !terms) return fail(MHE_ERR_ARG, "invalid argument");
-    *sums = reset ? c->rotsum_sums.exchange(0) : c->rotsum_sums.load();
-    *terms = reset ? c->rotsum_terms.exchange(0) : c->rotsum_terms.load();
-    return MHE_OK;
-}
-
-MHE_EXPORT int mhe_rotate_sum(mhe_ctx *c, int count, const uint64_t *const *in, const uint32_t *elts,
-                              const uint64_t *const *keys, const int *key_limbs, const int *group, int groups,
-                              uint64_t *const *out, int accumulate, int limbs, void *s)
-{
-    int r = check_limbs(c, limbs, 1);
-    if (r) return r;
-    if (count < 0 || groups < 0 || (count && (!in || !elts || !keys || !key_limbs || !group)) || (groups && !out))
-        return fail(MHE_ERR_ARG, "invalid argument");
-    hipStream_t st = S(s);
-    const int L = limbs;
-    const size_t n = c->n, ps = (size_t)L << c->log_n;
-    // group[] non-decreasing from 0 to groups - 1 without a gap: no group is empty
-    for (int i = 0, prev = 0; i < count; prev = group[i++])
-        if (group[i] != prev && !(i > 0 && group[i] == prev + 1)) return fail(MHE_ERR_ARG, "invalid argument");
-    if ((count ? group[count - 1] + 1 : 0) != groups) return fail(MHE_ERR_ARG, "invalid argument");
-    for (int g = 0; g < groups; g++)
-        if (!out[g]) return fail(MHE_ERR_ARG, "Galois key not present");
-    for (int i = 0; i < count; i++)
-    {
-        if (!in[i] || !keys[i]) return fail(MHE_ERR_ARG, "Galois key not present");
-        if (!(elts[i] & 1) || elts[i] >= 2 * c->n) return fail(MHE_ERR_ARG, "Galois element is not valid");
-        // every key is checked before the first launch, so a bad key leaves no output half-written
-        if (key_limbs[i] < limbs + 1 || key_limbs[i] > c->K)
-            return fail(MHE_ERR_ARG, "kswitch_keys is not valid for encryption parameters");
-    }
-    // outputs must be disjoint from every input and from each other (a group's output is written
-    // while later chunks still read their inputs)
-    for (int g = 0; g < groups; g++)
-    {
-        for (int i = 0; i < count; i++)
-            if (ranges_overlap(out[g], 2 * ps, in[i], 2 * ps))
-                return fail(MHE_ERR_ARG, "result cannot point to the same value as operand");
-        for (int h = 0; h < g; h++)
-            if (ranges_overlap(out[g], 2 * ps, out[h], 2 * ps))
-                return fail(MHE_ERR_ARG, "result cannot point to the same value as operand");
-    }
-    if (!count) return MHE_OK;
-    if (!c->galois_fused || !c->ks_fused)
-    {
-        // the debugging paths: rotate one by one and add
-        u64 *tmp = nullptr;
-        if (injected_alloc_failure(c) || mhe_internal_alloc((void **)&tmp, 2 * ps * sizeof(u64), st) != hipSuccess)
-            return fail(MHE_ERR_MEMORY, "device allocation failed");
-        for (int i = 0; i < count && !r; i++)
-        {
-            const bool first = (i == 0 || group[i] != group[i - 1]) && !accumulate;
-            u64 *o = out[group[i]];
-            r = mhe_apply_galois_to(c, in[i], first ? o : tmp, elts[i], keys[i], key_limbs[i], limbs, s);
-            if (!r && !first) r = launch_addsub(c, o, tmp, o, 2, limbs, 0, s);
-        }
-        (void)mhe_internal_free(tmp, st);
-        if (r) return r;
-        c->rotsum_sums += (unsigned long long)groups;
-        c->rotsum_terms += (unsigned long long)count;
-        return MHE_OK;
-    }
-    // all scratch before the first launch: a failed growth leaves every output as it was
-    Workspace *w;
-    if ((r = get_rotsum(c, st, std::min(count, MHE_MAXB), L, &w))) return r;
-    const size_t rs_per = (4 * (size_t)w->rs_limbs + 2) * n;
-    auto A_of = [&](int slot) { return w->rs_base.p + (size_t)slot * rs_per; };
-    auto T_of = [&](int slot) { return A_of(slot) + 2 * (size_t)(L + 1) * n; };
-    // rounds of at most MHE_MAXB groups: their entries, those of one key side by side (a launch of
-    // them shares the key stream, k_ks_row_mac share), in chunks of at most MHE_MAXB that cut across
-    // groups, then one ModDown forward NTT per limb for all of the round's groups
-    std::vector<int> order(count);
-    for (int i = 0; i < count; i++) order[i] = i;
-    int i0 = 0;
-    for (int g0 = 0; g0 < groups; g0 += MHE_MAXB)
-    {
-        const int G = std::min(MHE_MAXB, groups - g0);
-        int i1 = i0;
-        while (i1 < count && group[i1] < g0 + G) i1++;
-        std::stable_sort(order.begin() + i0, order.begin() + i1, [&](int a, int b) { return keys[a] < keys[b]; });
-        bool started[MHE_MAXB] = {}; // the round's groups that a chunk has written
-        for (int b0 = i0; b0 < i1; b0 += MHE_MAXB)
-        {
-            const int B = std::min(MHE_MAXB, i1 - b0);
-            // permuted (c0, c1) of every entry into its scratch, then the key switch of the permuted c1
-            // up to the key products (evaluator.cpp:2193-2214, 2281-2463)
-            GalPtrs gp{};
-            KsJob jobs[MHE_MAXB];
-            RotSumPtrs rp{};
-            int Z = 0, zslot[MHE_MAXB];
-            rp.B = B;
-            for (int e = 0; e < B; e++)
-            {
-                const int i = order[b0 + e];
-                gp.in[e] = in[i];
-                gp.out[e] = w->e[e].ct3;
-                gp.elt[e] = elts[i];
-                jobs[e] = KsJob{ nullptr, w->e[e].ct3 + ps, keys[i], key_limbs[i], nullptr };
-                rp.acc[e] = w->e[e].acc;
-                rp.perm[e] = w->e[e].ct3;
-                const int slot = group[i] - g0;
-                int z = 0;
-                while (z < Z && zslot[z] != slot) z++;
-                if (z == Z)
-                {
-                    zslot[Z++] = slot;
-                    rp.A[z] = A_of(slot);
-                    rp.T[z] = T_of(slot);
-                    rp.out[z] = out[group[i]];
-                    rp.first[z] = started[slot] ? 0 : 1; // the group's first chunk
-                    rp.write0[z] = (!started[slot] && !accumulate) ? 1 : 0;
-                    started[slot] = true;
-                }
-                rp.zof[e] = z;
-            }
-            const size_t total = 2 * ps;
-            count_op(c, MHE_OPK_GALOIS, L, 2ull * B);
-            hipLaunchKernelGGL(k_galois_b, dim3((unsigned)((total + 255) / 256), (unsigned)B), dim3(256), 0, st, gp,
-                               c->log_n, total);
-            HIP_LAUNCH_CHECK();
-            int special_inv_done = 0;
-            if ((r = run_switch_key_batch(c, jobs, B, L, st, 0, &special_inv_done))) return r;
-            // each entry's special limbs through their own inverse NTT, [0, 2P)
-            JobB<JobStrided> sj;
-            sj.per = 2;
-            for (int e = 0; e < B; e++) sj.j[e] = special_limbs(c, w->e[e].acc, L);
-            if (!special_inv_done) inv_row(sj, c->log_n, 2 * B, c->nm, st);
-            inv_col(sj, c->log_n, 2 * B, c->nm, st);
-            hipLaunchKernelGGL(k_rotsum_acc, dim3((unsigned)(n / 512), (unsigned)(2 * L), (unsigned)Z), dim3(256), 0, st,
-                               rp, c->primes, L, c->K, c->log_n);
-            HIP_LAUNCH_CHECK();
-        }
-        // the round's groups: T -> NTT(T) in place, then out += (A - NTT(T)) P^-1 (out[1] written
-        // when not accumulating)
-        JobB<JobFwdPlain> fc;
-        fc.per = 2 * L;
-        JobB<JobModDownRow> dr;
-        dr.per = 2 * L;
-        for (int z = 0; z < G; z++)
-        {
-            fc.j[z] = fwd_plain(c, T_of(z), T_of(z), L, 0);
-            dr.j[z] = JobModDownRow{ T_of(z), A_of(z), out[g0 + z], c->primes, c->tw, c->invq, L, c->K, c->log_n };
-            dr.j[z].fp = c->nm.fp ? 1 : 0;
-            dr.j[z].c1_write = accumulate ? 0 : 1;
-        }
-        fwd_col(fc, c->log_n, 2 * L * G, c->nm, st);
-        fwd_row(dr, c->log_n, 2 * L * G, c->nm, st);
-        HIP_LAUNCH_CHECK();
-        for (int z = 0; z < G; z++)
-        {
-            int terms = 0;
-            for (int i = i0; i < i1; i++) terms += group[i] == g0 + z;
-            count_op(c, MHE_OPK_ADDSUB, L, 2ull * (unsigned long long)(terms - 1 + (accumulate ? 1 : 0)));
-        }
-        i0 = i1;
-    }
-    c->rotsum_sums += (unsigned long long)groups;
-    c->rotsum_terms += (unsigned long long)count;
-    return MHE_OK;
-}
+// ------------------------------------------ batched rotations, hoisting and rotate-and-sum
+#include "rotate.h"
 
 MHE_EXPORT int mhe_rescale_batch(mhe_ctx *c, int count, const uint64_t *const *in, uint64_t *const *out, int size,
                                  int limbs, void *s)
@@ -2835,9 +1711,8 @@ MHE_EXPORT int mhe_rescale_batch(mhe_ctx *c, int count, const uint64_t *const *i
         if (!in[i] || !out[i]) return fail(MHE_ERR_ARG, "encrypted is not valid for encryption parameters");
         // an output may share no word with any entry's input or with another output: the last pass
         // writes out[i] while other workgroups of the same launch still read their inputs
-        for (int j = 0; j < count; j++)
-            if (ranges_overlap(out[i], ow, in[j], iw) || (j != i && ranges_overlap(out[i], ow, out[j], ow)))
-                return fail(MHE_ERR_ARG, "rescale output must not alias its input");
+        if (output_overlaps(out, i, count, ow, in, count, iw))
+            return fail(MHE_ERR_ARG, "rescale output must not alias its input");
     }
     for (int i0 = 0; i0 < count; i0 += MHE_MAXB)
     {
@@ -2858,8 +1733,7 @@ MHE_EXPORT int mhe_switch_key_batch(mhe_ctx *c, int count, uint64_t *const *ct, 
     {
         if (!ct[i] || !target[i] || !keys[i]) return fail(MHE_ERR_ARG, "target_iter");
         // every key before the first launch: the switches work in place, chunk by chunk
-        if (key_limbs[i] < limbs + 1 || key_limbs[i] > c->K)
-            return fail(MHE_ERR_ARG, "kswitch_keys is not valid for encryption parameters");
+        if ((r = check_key_limbs(c, key_limbs[i], limbs))) return r;
     }
     for (int i0 = 0; i0 < count; i0 += MHE_MAXB)
     {
@@ -2933,7 +1807,7 @@ MHE_EXPORT int mhe_hmult_batch(mhe_ctx *c, int count, const uint64_t *const *a, 
     int r = check_limbs(c, limbs, 2);
     if (r) return r;
     if (count < 0 || (count && (!a || !b || !out)) || !key) return fail(MHE_ERR_ARG, "invalid argument");
-    if (key_limbs < limbs + 1 || key_limbs > c->K) return fail(MHE_ERR_ARG, "kswitch_keys is not valid for encryption parameters");
+    if ((r = check_key_limbs(c, key_limbs, limbs))) return r;
     const size_t iw = (size_t)2 * limbs * c->n, ow = (size_t)2 * (limbs - 1) * c->n;
     for (int i = 0; i < count; i++)
     {
@@ -2986,13 +1860,5 @@ MHE_EXPORT int mhe_hmult(mhe_ctx *c, const uint64_t *a, const uint64_t *b, const
     int r = check_limbs(c, limbs, 2);
     if (r) return r;
     if (!a || !b || !key || !out) return fail(MHE_ERR_ARG, "invalid argument");
-    hipStream_t st = S(s);
-    Workspace *w;
-    r = get_ws(c, st, c->K - 1, &w);
-    if (r) return r;
-    if ((r = launch_tensor(c, a, b, w->ct3, limbs, a == b, st))) return r;
-    if (c->hmult_fused)
-        return run_switch_key(c, w->ct3, w->ct3 + ((size_t)2 * limbs << c->log_n), key, key_limbs, limbs, st, out);
-    if ((r = run_switch_key(c, w->ct3, w->ct3 + ((size_t)2 * limbs << c->log_n), key, key_limbs, limbs, st))) return r;
-    return run_rescale(c, w->ct3, out, 2, limbs, st);
+    return mhe_hmult_batch(c, 1, &a, &b, key, key_limbs, &out, limbs, s); // one entry: the same launches
 }
