@@ -154,6 +154,29 @@ __device__ __forceinline__ void fwd_stage_f(double (&v)[E], int gap, TwOf tw_of,
         }
 }
 
+// fwd_stage_f over two value vectors that take the same twiddles (two batch entries of one tile,
+// ntt.h k_ks_row_mac NE = 2): each twiddle is read once, into a local, and applied to both.
+template <int E, bool LAZY, class TwOf>
+__device__ __forceinline__ void fwd_stage_f2(double (&v0)[E], double (&v1)[E], int gap, TwOf tw_of, double q, double qinv)
+{
+#pragma unroll
+    for (int e = 0; e < E; e++)
+        if (!(e & gap))
+        {
+            const TwF w = *tw_of(e);
+            if (LAZY)
+            {
+                fwd_bfly_f_lazy(v0[e], v0[e + gap], w, q);
+                fwd_bfly_f_lazy(v1[e], v1[e + gap], w, q);
+            }
+            else
+            {
+                fwd_bfly_f(v0[e], v0[e + gap], w, q, qinv);
+                fwd_bfly_f(v1[e], v1[e + gap], w, q, qinv);
+            }
+        }
+}
+
 template <int E, class TwOf>
 __device__ __forceinline__ void inv_stage_f(double (&v)[E], int gap, TwOf tw_of, double q, double qinv)
 {

@@ -127,6 +127,12 @@ static int ks_shared_key(const mhe_ctx *c, const KsJob *jobs, int B)
     return 1;
 }
 
+// The pairing switch and counters of the fused MAC's launches (ntt.h KsPair).
+static KsPair ks_pair_of(mhe_ctx *c)
+{
+    return KsPair{ c->ks_pair, &c->ks_paired, &c->ks_single };
+}
+
 // Step 4 of a (batched) key switch, the ModDown (evaluator.cpp:2466-2524), over the key inner
 // products in w->e[e].acc (or accs[e]): ct_e += ModDown(acc_e), or with rescale_out the fused HMult tail (see
 // run_switch_key_batch).  special_inv_done: the key MAC already ran the special limbs' inverse
@@ -225,8 +231,10 @@ static void run_moddown(mhe_ctx *c, const KsJob *jobs, int B, int L, Workspace *
 // front != nullptr (mhe_rotate_sum; fused key MAC only): stop before the ModDown, the key products
 // left in the entries' scratch (w->e[e].acc), ct untouched; *front = the key MAC already ran the
 // special limbs' inverse row pass.
+// pair = 0: the key MAC runs one entry per workgroup whatever the context's switch says (the hoisting
+// check recomputes by the kept one-entry kernel).
 static int run_switch_key_batch(mhe_ctx *c, const KsJob *jobs, int B, int L, hipStream_t st, int c1_write = 0,
-                                int *front = nullptr)
+                                int *front = nullptr, int pair = 1)
 {
     if (B < 1 || B > MHE_MAXB) return fail(MHE_ERR_ARG, "key switch: batch size out of range");
     // mhe_debug_fail_switch's countdown (tests): this launch sequence fails before its first launch
@@ -244,7 +252,7 @@ static int run_switch_key_batch(mhe_ctx *c, const KsJob *jobs, int B, int L, hip
     {
         // the separate-MAC debugging path runs one entry at a time
         for (int e = 0; e < B; e++)
-            if (int r = run_switch_key_batch(c, jobs + e, 1, L, st, c1_write)) return r;
+            if (int r = run_switch_key_batch(c, jobs + e, 1, L, st, c1_write, nullptr, pair)) return r;
         return MHE_OK;
     }
     int kpack = 1, r;
@@ -280,8 +288,10 @@ static int run_switch_key_batch(mhe_ctx *c, const KsJob *jobs, int B, int L, hip
         }
         timing_end(tc, st);
         hipEvent_t *tm = timing_slot(c, w, TK_KS_ROW_MAC, st);
+        KsPair pr = ks_pair_of(c);
+        if (!pair) pr.on = 0;
         special_inv_done = ks_row_mac_chunk(kp, B, c->primes, c->tw, L, c->K, log_n, c->nm_ks, 0, L + 1, pack, kpack,
-                                            ks_shared_key(c, jobs, B), c->itw, 1, st);
+                                            ks_shared_key(c, jobs, B), pr, c->itw, 1, st);
         timing_end(tm, st);
     }
     else

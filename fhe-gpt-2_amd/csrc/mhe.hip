@@ -278,6 +278,9 @@ struct mhe_ctx
     int timing = 0;      // record HIP events around the key-switch kernels (mhe_ctx_set_timing)
     int hmult_fused = 1; // HMult: ModDown fused with the rescale (MHE_HMULT_FUSED=0: separate)
     int ks_share = 1;    // batched key switches sharing one key: XCD-grouped entries (MHE_KS_SHARE=0: off)
+    // shared-key launches at n = 2^16 (FP64): two entries per workgroup (k_ks_row_mac NE = 2; MHE_KS_PAIR=0: one)
+    int ks_pair = 1;
+    std::atomic<unsigned long long> ks_paired{ 0 }, ks_single{ 0 }; // mhe_ks_pair_stats
     int ks_colgroups = 9; // ModUp column pass: output-prime groups per digit (MHE_KS_COLGROUPS; 0 = one job per (I, J))
     int ks_pack = 1; // n = 2^16: ModUp intermediate of primes < 2^48 stored in 48 bits (MHE_KS_PACK=0: 64 bits)
     int icol_fused = 1; // ModDown / rescale: inverse column pass fused into the lift column pass (MHE_ICOL_FUSED=0: separate)
@@ -810,6 +813,7 @@ MHE_EXPORT int mhe_ctx_create(mhe_ctx **out, int log_n, const uint64_t *moduli, 
     if (const char *f = getenv("MHE_KS_FUSED")) c->ks_fused = atoi(f);
     if (const char *f = getenv("MHE_HMULT_FUSED")) c->hmult_fused = atoi(f);
     if (const char *f = getenv("MHE_KS_SHARE")) c->ks_share = atoi(f);
+    if (const char *f = getenv("MHE_KS_PAIR")) c->ks_pair = atoi(f);
     if (const char *f = getenv("MHE_KS_COLGROUPS")) c->ks_colgroups = atoi(f);
     if (const char *f = getenv("MHE_KS_PACK")) c->ks_pack = atoi(f);
     if (const char *f = getenv("MHE_GALOIS_FUSED")) c->galois_fused = atoi(f);

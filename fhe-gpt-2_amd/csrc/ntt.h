@@ -20,6 +20,7 @@
 // and load()/store() hooks.  Key switching and rescale fuse their digit lift / (c - t)*q^-1
 // epilogues into these hooks, so the lifted digits never take an extra HBM round trip.
 #pragma once
+#include <atomic>
 #include <type_traits>
 
 #include "arith.h"
@@ -256,6 +257,12 @@ struct NttArithF
     __device__ void fwd_tab(T (&v)[E], int gap, const TW *tab, Ix ix) const
     {
         fwd_stage_f<E, LAZY>(v, gap, [&](int e) { return &tab[ix(e)]; }, q, qinv);
+    }
+    // fwd_tab on two vectors with one read of each twiddle (fwd_stage_f2)
+    template <int E, class Ix>
+    __device__ void fwd_tab2(T (&v0)[E], T (&v1)[E], int gap, const TW *tab, Ix ix) const
+    {
+        fwd_stage_f2<E, LAZY>(v0, v1, gap, [&](int e) { return &tab[ix(e)]; }, q, qinv);
     }
     template <int E, class Ix>
     __device__ void inv(T (&v)[E], int gap, Ix ix) const
@@ -1519,6 +1526,9 @@ template <class Job> static inline void inv_col(const Job &j, int log_n, int job
 //     key streams, which are issued one digit (digits) / one NTT (key) ahead.
 //   * Barriers wait on LDS only (s_waitcnt lgkmcnt(0) + s_barrier): __syncthreads() would
 //     also drain vmcnt and serialise the prefetch (cdna_hip_programming.md §8).
+//   * NE = 2 (FP64, n = 2^16, a launch whose entries share the key): one workgroup
+//     takes the same tile of two batch entries, blockIdx.z the pair.  Key limbs and twiddles are
+//     read once per digit for both; 242 VGPRs, 64 KB of LDS, 2 waves per SIMD.
 template <int LOGR>
 struct RowMacShape
 {
@@ -1551,18 +1561,36 @@ __device__ __forceinline__ void row_stages(typename A::T (&v)[8], u32 t, int b_l
         ar.template fwd_tab<8>(v, 1 << (LOGR - 1 - s - b_lo), twl, // gap in slot units
                                [&](int e) { return twz((1u << s) + (lay(t, e, b_lo) >> (LOGR - s))); });
 }
+// row_stages of two batch entries' vectors of one tile: every twiddle is read from LDS once
+template <int LOGR, class A>
+__device__ __forceinline__ void row_stages2(typename A::T (&v0)[8], typename A::T (&v1)[8], u32 t, int b_lo, int s0,
+                                            int s1, const typename A::TW *twl, const A &ar)
+{
+#pragma unroll
+    for (int s = s0; s < s1; s++)
+        ar.template fwd_tab2<8>(v0, v1, 1 << (LOGR - 1 - s - b_lo), twl,
+                                [&](int e) { return twz((1u << s) + (lay(t, e, b_lo) >> (LOGR - s))); });
+}
 
 // waves per SIMD the FP64 fused MAC at n = 2^16 is compiled for: 168 VGPRs, one LDS transpose buffer
 // (48 KB).  With the loads at the top of each digit (the sched_barrier in `step`) C2's k_ks_row_mac
 // 2743 -> 2698 us, ResNet-level ops equal (profiles/r06n); without them 3 waves were equal on C2 and 2 %
 // slower on single key switches (r06c)
 constexpr int MHE_KS_OCC = 3;
-template <int LOGR, bool FP, bool MIX = false>
-__global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8) ? MHE_KS_OCC : 2) void k_ks_row_mac(KsPtrs P, const PrimeDev *__restrict__ primes,
+// NE: batch entries per workgroup.  NE = 2 (FP64 without MIX at n = 2^16 only; ks_row_mac_a chooses
+// it): the workgroup runs the same tile of entries 2 bz and 2 bz + 1, which share the key and carry
+// no run_if flag.  One digit loop serves both: the key limbs are loaded once and converted once per
+// digit, each twiddle is read from LDS once (row_stages2), and two digit vectors go through the
+// same butterflies into two accumulator sets -- per entry the arithmetic, and every output word, is
+// that of NE = 1.  Twice the accumulators, values and prefetched digits: 2 waves per SIMD, and one
+// transpose buffer per entry (64 KB of LDS, 2 workgroups per CU).
+template <int LOGR, bool FP, bool MIX = false, int NE = 1>
+__global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8 && NE == 1) ? MHE_KS_OCC : 2) void k_ks_row_mac(KsPtrs P, const PrimeDev *__restrict__ primes,
                                                        const Tw *__restrict__ tw_all, int L, int K, int log_n,
                                                        long long twd, int I0, int pack, int kpack, int share,
                                                        const Tw *__restrict__ itw_all, long long tinv, int inv_special)
 {
+    static_assert(NE == 1 || (NE == 2 && FP && !MIX && LOGR == 8), "two entries per workgroup: FP64, n = 2^16 only");
     // tile (bx = column block group, by = output prime) and batch entry bz.  With `share` (every
     // entry reads the same key, gridDim.x * gridDim.y a multiple of 8) the linear workgroup ids are
     // dealt so that the gridDim.z entries of one tile are ids 8 apart and adjacent in dispatch
@@ -1579,14 +1607,21 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8) ? MHE_KS_OCC : 2) vo
         bx = tile % X;
         by = tile / X;
     }
-    if (P.run_if[bz] && !*P.run_if[bz]) return; // uniform, before any barrier
-    // batch entry bz: inter [cnt][L][n] column-pass output, target [L][n] NTT form,
-    // key [digits][2][key_limbs][n], acc [2][L+1][n]
-    const u64 *__restrict__ inter = P.inter[bz];
-    const u64 *__restrict__ target = P.target[bz];
-    const u64 *__restrict__ key = P.key[bz];
-    u64 *__restrict__ acc = P.acc[bz];
-    const int key_limbs = P.key_limbs[bz];
+    if constexpr (NE == 1)
+        if (P.run_if[bz] && !*P.run_if[bz]) return; // uniform, before any barrier
+    // batch entries NE bz + x: inter [cnt][L][n] column-pass output, target [L][n] NTT form,
+    // key [digits][2][key_limbs][n] (one for all NE entries), acc [2][L+1][n]
+    const u64 *__restrict__ inter[NE];
+    const u64 *__restrict__ target[NE];
+    u64 *__restrict__ acc[NE];
+#pragma unroll
+    for (int x = 0; x < NE; x++) inter[x] = P.inter[NE * bz + x];
+#pragma unroll
+    for (int x = 0; x < NE; x++) target[x] = P.target[NE * bz + x];
+    const u64 *__restrict__ key = P.key[NE * bz];
+#pragma unroll
+    for (int x = 0; x < NE; x++) acc[x] = P.acc[NE * bz + x];
+    const int key_limbs = P.key_limbs[NE * bz];
     using SH = RowMacShape<LOGR>;
     using A = NttArith<FP>;
     using T = typename A::T;
@@ -1600,8 +1635,9 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8) ? MHE_KS_OCC : 2) vo
     constexpr int BK = 0;
     // one transpose buffer is enough (every transpose stays inside one wave and a wave's LDS
     // operations complete in order; the fences only stop the compiler from reordering them):
-    // 48 KB per workgroup fits 3 workgroups per CU, two buffers (64 KB) only 2
-    constexpr int XCH = (FP && !MIX && LOGR == 8) ? 1 : 2;
+    // 48 KB per workgroup fits 3 workgroups per CU, two buffers (64 KB) only 2.  NE = 2: one buffer
+    // per entry, so the two entries' transposes do not wait on each other
+    constexpr int XCH = NE == 2 ? 2 : (FP && !MIX && LOGR == 8) ? 1 : 2;
     __shared__ T xch[XCH][S * R];
     __shared__ TW twl[S * R];
     const int j0 = 0, j1 = L;
@@ -1637,7 +1673,13 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8) ? MHE_KS_OCC : 2) vo
             }
         }
         const TW *mytw = &twl_a[sl * R];
-        T *x0 = reinterpret_cast<T *>(&xch[0][sl * R]), *x1 = reinterpret_cast<T *>(&xch[XCH - 1][sl * R]);
+        T *x0[NE], *x1[NE]; // per entry: the buffers of the first and of the second transpose
+#pragma unroll
+        for (int x = 0; x < NE; x++)
+        {
+            x0[x] = reinterpret_cast<T *>(&xch[NE == 2 ? x : 0][sl * R]);
+            x1[x] = reinterpret_cast<T *>(&xch[NE == 2 ? x : XCH - 1][sl * R]);
+        }
         // FP: the key inner products run in FP64 as well (fp_mulmod_gen); with q < 2^47 and
         // 1.25 (j1 - j0) q < 2^53 (LZ, chosen below) the digits stay unreduced and the products
         // (|.| < 1.25q each) sum exactly, otherwise digits are reduced and the sums every second
@@ -1645,15 +1687,17 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8) ? MHE_KS_OCC : 2) vo
         // accumulation, one Barrett reduction at the end (evaluator.cpp:2412-2462).
         constexpr bool LZ = std::is_same<AR, NttArithF<true>>::value;
         using AccT = typename std::conditional<FPA, double, Acc128>::type;
-        AccT a0[8], a1[8];
+        AccT a0[NE][8], a1[NE][8];
 #pragma unroll
-        for (int e = 0; e < 8; e++)
-        {
-            if constexpr (FPA)
-                a0[e] = a1[e] = 0.0;
-            else
-                a0[e] = a1[e] = Acc128{ 0, 0 };
-        }
+        for (int x = 0; x < NE; x++)
+#pragma unroll
+            for (int e = 0; e < 8; e++)
+            {
+                if constexpr (FPA)
+                    a0[x][e] = a1[x][e] = 0.0;
+                else
+                    a0[x][e] = a1[x][e] = Acc128{ 0, 0 };
+            }
 
         // Digit J of this output prime is the input limb itself (J == I, already NTT form) or the
         // column-pass output, packed (tile16) when the column pass packed it.  The input limb is
@@ -1677,14 +1721,14 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8) ? MHE_KS_OCC : 2) vo
             // plane and in the 16-bit plane (which starts at 4n)
             const u32 off_lo = 4u * tile16(base + lay(t, 0, B_A));
             const u32 off_hi = 4u * (u32)n + 2u * tile16h(base + lay(t, 0, B_A));
-            auto load_inter = [&](int J, u64 (&v)[8]) {
+            auto load_inter = [&](int x, int J, u64 (&v)[8]) {
                 if constexpr (PK && LOGR == 8)
                 {
                     // buffer loads: the digit's slot as a descriptor built from uniform values and
                     // loop-invariant 32-bit lane offsets (global loads rebuilt a 64-bit address per
                     // load and digit).  At n = 2^16 a lane's residues e = 0..7 are one column block
                     // apart in both planes: tile16 / tile16h of base + lay(t, e, 5) grow by 512 e.
-                    const u64 *slot = inter + ((size_t)(I - I0) * L + J) * n;
+                    const u64 *slot = inter[x] + ((size_t)(I - I0) * L + J) * n;
                     const __amdgpu_buffer_rsrc_t rs =
                         __builtin_amdgcn_make_buffer_rsrc(const_cast<u64 *>(slot), 0, (int)(8 * n), 0x00020000);
                     constexpr int AUX = ((MHE_NT >> 2) & 1) ? 2 : 0; // nt
@@ -1699,7 +1743,7 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8) ? MHE_KS_OCC : 2) vo
                 }
                 else if constexpr (PK)
                 {
-                    const u32 *lo = reinterpret_cast<const u32 *>(inter + ((size_t)(I - I0) * L + J) * n);
+                    const u32 *lo = reinterpret_cast<const u32 *>(inter[x] + ((size_t)(I - I0) * L + J) * n);
                     const unsigned short *hi = reinterpret_cast<const unsigned short *>(lo + n);
 #pragma unroll
                     for (int e = 0; e < 8; e++)
@@ -1710,7 +1754,7 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8) ? MHE_KS_OCC : 2) vo
                 }
                 else
                 {
-                    const u64 *src = inter + ((size_t)(I - I0) * L + J) * n + base;
+                    const u64 *src = inter[x] + ((size_t)(I - I0) * L + J) * n + base;
 #pragma unroll
                     for (int e = 0; e < 8; e++) v[e] = ld_nt<2>(&src[lay(t, e, B_A)]);
                 }
@@ -1746,22 +1790,29 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8) ? MHE_KS_OCC : 2) vo
             };
             // d (the digit in the coalesced layout, NTT form) times both key limbs; `odd` is the
             // parity of the digits taken so far (the non-lazy FP sums are reduced every second one)
-            auto mac = [&](const T (&d)[8], const u64 (&ka)[8], const u64 (&kb)[8], bool odd) {
+            // (every entry of the workgroup against the same key doubles, converted once)
+            auto mac = [&](const T (&d)[NE][8], const u64 (&ka)[8], const u64 (&kb)[8], bool odd) {
                 if constexpr (FPA)
                 {
 #pragma unroll
                     for (int e = 0; e < 8; e++)
                     {
-                        const double dv = LZ ? d[e] : fp_reduce(d[e], ar.q, ar.qinv);
+                        double dv[NE];
+#pragma unroll
+                        for (int x = 0; x < NE; x++) dv[x] = LZ ? d[x][e] : fp_reduce(d[x][e], ar.q, ar.qinv);
                         // canonical key residues
                         const double k0v = KF == 1 ? key_word_f(ka[e]) : fp_from_u52(ka[e]);
                         const double k1v = KF == 1 ? key_word_f(kb[e]) : fp_from_u52(kb[e]);
-                        a0[e] += fp_mulmod_gen(dv, k0v, ar.q, ar.qinv);
-                        a1[e] += fp_mulmod_gen(dv, k1v, ar.q, ar.qinv);
-                        if (!LZ && odd)
+#pragma unroll
+                        for (int x = 0; x < NE; x++)
                         {
-                            a0[e] = fp_reduce(a0[e], ar.q, ar.qinv);
-                            a1[e] = fp_reduce(a1[e], ar.q, ar.qinv);
+                            a0[x][e] += fp_mulmod_gen(dv[x], k0v, ar.q, ar.qinv);
+                            a1[x][e] += fp_mulmod_gen(dv[x], k1v, ar.q, ar.qinv);
+                            if (!LZ && odd)
+                            {
+                                a0[x][e] = fp_reduce(a0[x][e], ar.q, ar.qinv);
+                                a1[x][e] = fp_reduce(a1[x][e], ar.q, ar.qinv);
+                            }
                         }
                     }
                 }
@@ -1770,24 +1821,33 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8) ? MHE_KS_OCC : 2) vo
 #pragma unroll
                     for (int e = 0; e < 8; e++)
                     {
-                        mac128(a0[e], d[e], KF == 1 ? key_word_u(ka[e]) : ka[e]);
-                        mac128(a1[e], d[e], KF == 1 ? key_word_u(kb[e]) : kb[e]);
+                        mac128(a0[0][e], d[0][e], KF == 1 ? key_word_u(ka[e]) : ka[e]);
+                        mac128(a1[0][e], d[0][e], KF == 1 ? key_word_u(kb[e]) : kb[e]);
                     }
                 }
             };
             // the row stages of a column-pass output (J != I)
-            auto ntt_digit = [&](const u64 (&vin)[8], T (&d)[8]) {
-                T w[8];
+            auto ntt_digit = [&](const u64 (&vin)[NE][8], T (&d)[NE][8]) {
+                T w[NE][8];
 #pragma unroll
-                for (int e = 0; e < 8; e++)
-                {
-                    // the column-pass output: FP and packed, a centred 48-bit residue (fp_to_s48);
-                    // otherwise canonical
-                    if constexpr (FPA)
-                        w[e] = PK ? fp_from_s48(vin[e]) : ar.in52(vin[e]);
+                for (int x = 0; x < NE; x++)
+#pragma unroll
+                    for (int e = 0; e < 8; e++)
+                    {
+                        // the column-pass output: FP and packed, a centred 48-bit residue (fp_to_s48);
+                        // otherwise canonical
+                        if constexpr (FPA)
+                            w[x][e] = PK ? fp_from_s48(vin[x][e]) : ar.in52(vin[x][e]);
+                        else
+                            w[x][e] = ar.in52(vin[x][e]);
+                    }
+                // forward stages [s0, s1) of every entry's vector, each twiddle read once
+                auto stages = [&](int b_lo, int first, int end) {
+                    if constexpr (NE == 2 && FPA) // (the integer arithmetic never runs with NE = 2)
+                        row_stages2<LOGR>(w[0], w[1], t, b_lo, first, end, mytw, ar);
                     else
-                        w[e] = ar.in52(vin[e]);
-                }
+                        row_stages<LOGR>(w[0], t, b_lo, first, end, mytw, ar);
+                };
                 // LDS slots of the transposes: swz is linear over GF(2) and lay(t, e, b) is the
                 // disjoint OR of a lane part and e << b, so slot = swz(lane part) ^ swz(e << b).  The
                 // non-lazy sweep (more live values) recomputes the XORs from three per-lane bases
@@ -1796,60 +1856,81 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8) ? MHE_KS_OCC : 2) vo
                 u32 sa = swz(lay(t, 0, B_A)), sb = swz(lay(t, 0, B_B)), s0 = swz(lay(t, 0, 0));
                 if constexpr (!LZ) asm volatile("" : "+v"(sa), "+v"(sb), "+v"(s0));
                 auto slot = [&](u32 lane_part, int e, int b) { return lane_part ^ swz((u32)e << b); };
-                row_stages<LOGR>(w, t, B_A, 0, 3, mytw, ar);
+                stages(B_A, 0, 3);
                 wave_lds_fence(); // the previous digit's reads of x0 come first
 #pragma unroll
-                for (int e = 0; e < 8; e++) x0[slot(sa, e, B_A)] = w[e];
+                for (int x = 0; x < NE; x++)
+#pragma unroll
+                    for (int e = 0; e < 8; e++) x0[x][slot(sa, e, B_A)] = w[x][e];
                 wave_lds_fence();
 #pragma unroll
-                for (int e = 0; e < 8; e++) w[e] = x0[slot(sb, e, B_B)];
-                row_stages<LOGR>(w, t, B_B, 3, 6, mytw, ar);
+                for (int x = 0; x < NE; x++)
+#pragma unroll
+                    for (int e = 0; e < 8; e++) w[x][e] = x0[x][slot(sb, e, B_B)];
+                stages(B_B, 3, 6);
                 if (LOGR > 6)
                 {
                     wave_lds_fence();
 #pragma unroll
-                    for (int e = 0; e < 8; e++) x1[slot(sb, e, B_B)] = w[e];
+                    for (int x = 0; x < NE; x++)
+#pragma unroll
+                        for (int e = 0; e < 8; e++) x1[x][slot(sb, e, B_B)] = w[x][e];
                     wave_lds_fence();
 #pragma unroll
-                    for (int e = 0; e < 8; e++) w[e] = x1[slot(s0, e, 0)];
-                    row_stages<LOGR>(w, t, 0, 6, LOGR, mytw, ar);
+                    for (int x = 0; x < NE; x++)
+#pragma unroll
+                        for (int e = 0; e < 8; e++) w[x][e] = x1[x][slot(s0, e, 0)];
+                    stages(0, 6, LOGR);
                 }
                 // already the keys' layout (integer: canonical digits keep the 128-bit sums
                 // exact for any digit count below 2^8)
 #pragma unroll
-                for (int e = 0; e < 8; e++)
-                {
-                    if constexpr (FPA)
-                        d[e] = w[e];
-                    else
-                        d[e] = ar.canon(w[e]);
-                }
+                for (int x = 0; x < NE; x++)
+#pragma unroll
+                    for (int e = 0; e < 8; e++)
+                    {
+                        if constexpr (FPA)
+                            d[x][e] = w[x][e];
+                        else
+                            d[x][e] = ar.canon(w[x][e]);
+                    }
             };
-            u64 ka[8], kb[8], va[8], vb[8];
-            if (nd > 0) load_inter(digit_of(0), va); // nd == 0: one data limb, output prime 0
-            lds_barrier();                             // twiddles visible
+            u64 ka[8], kb[8], va[NE][8], vb[NE][8];
+            if (nd > 0) // nd == 0: one data limb, output prime 0
+            {
+#pragma unroll
+                for (int x = 0; x < NE; x++) load_inter(x, digit_of(0), va[x]);
+            }
+            lds_barrier(); // twiddles visible
             if (has_self)
             {
                 // the input limb of digit I: a canonical ciphertext limb, already NTT form
-                const u64 *src = target + (size_t)I * n + base;
 #pragma unroll
-                for (int e = 0; e < 8; e++) vb[e] = ld_nt<2>(&src[lay(t, e, BK)]);
+                for (int x = 0; x < NE; x++)
+                {
+                    const u64 *src = target[x] + (size_t)I * n + base;
+#pragma unroll
+                    for (int e = 0; e < 8; e++) vb[x][e] = ld_nt<2>(&src[lay(t, e, BK)]);
+                }
                 load_key(I, ka, kb);
-                T d[8];
+                T d[NE][8];
 #pragma unroll
-                for (int e = 0; e < 8; e++) d[e] = ar.in52(vb[e]);
+                for (int x = 0; x < NE; x++)
+#pragma unroll
+                    for (int e = 0; e < 8; e++) d[x][e] = ar.in52(vb[x][e]);
                 mac(d, ka, kb, false);
             }
             const int c0 = has_self ? 1 : 0; // digits taken before the loop
-            auto step = [&](int u, const u64 (&cur)[8], u64 (&nxt)[8]) {
+            auto step = [&](int u, const u64 (&cur)[NE][8], u64 (&nxt)[NE][8]) {
                 load_key(digit_of(u), ka, kb);
-                load_inter(digit_of(u + 1 < nd ? u + 1 : u), nxt); // one digit ahead
+#pragma unroll
+                for (int x = 0; x < NE; x++) load_inter(x, digit_of(u + 1 < nd ? u + 1 : u), nxt[x]); // one digit ahead
                 // issue both streams before the digit's transform: left to the scheduler, they went
                 // out a quarter into it and the copy of the prefetched digit at the end of the step
                 // waited for them (vmcnt(0)).  FP64 without MIX only: the integer and MIX variants
                 // spill already and spilled more
                 if constexpr (FP && !MIX) __builtin_amdgcn_sched_barrier(0);
-                T d[8];
+                T d[NE][8];
                 ntt_digit(cur, d);
                 mac(d, ka, kb, ((u + c0) & 1) != 0);
             };
@@ -1857,7 +1938,9 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8) ? MHE_KS_OCC : 2) vo
             {
                 step(u, va, vb);
 #pragma unroll
-                for (int e = 0; e < 8; e++) va[e] = vb[e];
+                for (int x = 0; x < NE; x++)
+#pragma unroll
+                    for (int e = 0; e < 8; e++) va[x][e] = vb[x][e];
             }
         };
         using F0 = std::integral_constant<int, 0>;
@@ -1875,102 +1958,109 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8) ? MHE_KS_OCC : 2) vo
             else if (kfmt == 2) loop(std::false_type{}, F2{});
             else loop(std::false_type{}, F0{});
         }
-        u64 *o0 = acc + (size_t)I * n + base;
-        u64 *o1 = o0 + (size_t)(L + 1) * n;
-        if (inv_special && I == L) // uniform per workgroup
-        {
-            // The ModDown's first step, the inverse row pass of the special limbs (k_inv_row with
-            // JobStrided, evaluator.cpp:2466-2475), on this workgroup's rows: its accumulators are
-            // whole 2^LOGR-blocks, so the Gentleman-Sande stages LOGR-1 .. 0 run here -- in-lane
-            // position bits 0-2, then 3-5, then the rest, with the same swizzled in-wave transposes
-            // -- and the separate launch (and its HBM round trip) disappears.  Canonical output.
-            using AI = NttArith<FPA>;
-            const AI ai(p, itw_all + ((size_t)pi << log_n), tinv);
-            const u32 rbi = R1 + b;
-            auto tr = [&](T (&w)[8], int from, int to) {
-                wave_lds_fence();
+        // the epilogue, entry by entry (NE = 2: the second entry's after the first's; its share of
+        // the kernel is small and the values of one entry at a time keep the registers low)
+        auto finish = [&](auto xc) {
+            constexpr int x = decltype(xc)::value;
+            u64 *o0 = acc[x] + (size_t)I * n + base;
+            u64 *o1 = o0 + (size_t)(L + 1) * n;
+            if (inv_special && I == L) // uniform per workgroup
+            {
+                // The ModDown's first step, the inverse row pass of the special limbs (k_inv_row with
+                // JobStrided, evaluator.cpp:2466-2475), on this workgroup's rows: its accumulators are
+                // whole 2^LOGR-blocks, so the Gentleman-Sande stages LOGR-1 .. 0 run here -- in-lane
+                // position bits 0-2, then 3-5, then the rest, with the same swizzled in-wave transposes
+                // -- and the separate launch (and its HBM round trip) disappears.  Canonical output.
+                using AI = NttArith<FPA>;
+                const AI ai(p, itw_all + ((size_t)pi << log_n), tinv);
+                const u32 rbi = R1 + b;
+                auto tr = [&](T (&w)[8], int from, int to) {
+                    wave_lds_fence();
 #pragma unroll
-                for (int e = 0; e < 8; e++) x0[swz(lay(t, e, from))] = w[e];
-                wave_lds_fence();
+                    for (int e = 0; e < 8; e++) x0[x][swz(lay(t, e, from))] = w[e];
+                    wave_lds_fence();
 #pragma unroll
-                for (int e = 0; e < 8; e++) w[e] = x0[swz(lay(t, e, to))];
-            };
-            auto stages = [&](T (&w)[8], int b_lo, int s_hi, int s_lo) {
+                    for (int e = 0; e < 8; e++) w[e] = x0[x][swz(lay(t, e, to))];
+                };
+                auto stages = [&](T (&w)[8], int b_lo, int s_hi, int s_lo) {
 #pragma unroll
-                for (int s = s_hi; s >= s_lo; s--)
-                    ai.template inv<8>(w, 1 << (LOGR - 1 - s - b_lo),
-                                       [&](int e) { return (rbi << s) + (lay(t, e, b_lo) >> (LOGR - s)); });
-            };
-            auto inv_rows = [&](T (&w)[8]) {
-                stages(w, 0, LOGR - 1, LOGR - 3);
-                tr(w, 0, 3);
-                stages(w, 3, LOGR - 4, LOGR > 6 ? LOGR - 6 : 0);
-                if (LOGR > 6)
+                    for (int s = s_hi; s >= s_lo; s--)
+                        ai.template inv<8>(w, 1 << (LOGR - 1 - s - b_lo),
+                                           [&](int e) { return (rbi << s) + (lay(t, e, b_lo) >> (LOGR - s)); });
+                };
+                auto inv_rows = [&](T (&w)[8]) {
+                    stages(w, 0, LOGR - 1, LOGR - 3);
+                    tr(w, 0, 3);
+                    stages(w, 3, LOGR - 4, LOGR > 6 ? LOGR - 6 : 0);
+                    if (LOGR > 6)
+                    {
+                        tr(w, 3, B_A);
+                        stages(w, B_A, LOGR - 7, 0);
+                    }
+                };
+                T w0[8], w1[8];
+#pragma unroll
+                for (int e = 0; e < 8; e++)
                 {
-                    tr(w, 3, B_A);
-                    stages(w, B_A, LOGR - 7, 0);
+                    if constexpr (FPA)
+                    {
+                        w0[e] = fp_reduce(a0[x][e], ar.q, ar.qinv);
+                        w1[e] = fp_reduce(a1[x][e], ar.q, ar.qinv);
+                    }
+                    else
+                    {
+                        w0[e] = barrett128(a0[x][e].lo, a0[x][e].hi, p);
+                        w1[e] = barrett128(a1[x][e].lo, a1[x][e].hi, p);
+                    }
                 }
-            };
-            T w0[8], w1[8];
+                inv_rows(w0);
+                inv_rows(w1);
+#pragma unroll
+                for (int e = 0; e < 8; e++)
+                {
+                    const u32 r = lay(t, e, B_A);
+                    o0[r] = ai.canon(w0[e]);
+                    o1[r] = ai.canon(w1[e]);
+                }
+                return;
+            }
+            u64 c0v[8], c1v[8]; // canonical key products, layout BK
 #pragma unroll
             for (int e = 0; e < 8; e++)
             {
                 if constexpr (FPA)
                 {
-                    w0[e] = fp_reduce(a0[e], ar.q, ar.qinv);
-                    w1[e] = fp_reduce(a1[e], ar.q, ar.qinv);
+                    c0v[e] = fp_canon(a0[x][e], ar.q, ar.qinv);
+                    c1v[e] = fp_canon(a1[x][e], ar.q, ar.qinv);
                 }
                 else
                 {
-                    w0[e] = barrett128(a0[e].lo, a0[e].hi, p);
-                    w1[e] = barrett128(a1[e].lo, a1[e].hi, p);
+                    c0v[e] = barrett128(a0[x][e].lo, a0[x][e].hi, p);
+                    c1v[e] = barrett128(a1[x][e].lo, a1[x][e].hi, p);
                 }
             }
-            inv_rows(w0);
-            inv_rows(w1);
+            // one transpose per workgroup to the coalesced layout for the stores
+            u64 *xu = reinterpret_cast<u64 *>(x0[x]);
+            auto back = [&](u64 (&v)[8]) {
+                wave_lds_fence();
+#pragma unroll
+                for (int e = 0; e < 8; e++) xu[swz(lay(t, e, BK))] = v[e];
+                wave_lds_fence();
+#pragma unroll
+                for (int e = 0; e < 8; e++) v[e] = xu[swz(lay(t, e, B_A))];
+            };
+            back(c0v);
+            back(c1v);
 #pragma unroll
             for (int e = 0; e < 8; e++)
             {
                 const u32 r = lay(t, e, B_A);
-                o0[r] = ai.canon(w0[e]);
-                o1[r] = ai.canon(w1[e]);
+                o0[r] = c0v[e];
+                o1[r] = c1v[e];
             }
-            return;
-        }
-        u64 c0v[8], c1v[8]; // canonical key products, layout BK
-#pragma unroll
-        for (int e = 0; e < 8; e++)
-        {
-            if constexpr (FPA)
-            {
-                c0v[e] = fp_canon(a0[e], ar.q, ar.qinv);
-                c1v[e] = fp_canon(a1[e], ar.q, ar.qinv);
-            }
-            else
-            {
-                c0v[e] = barrett128(a0[e].lo, a0[e].hi, p);
-                c1v[e] = barrett128(a1[e].lo, a1[e].hi, p);
-            }
-        }
-        // one transpose per workgroup to the coalesced layout for the stores
-        u64 *xu = reinterpret_cast<u64 *>(x0);
-        auto back = [&](u64 (&v)[8]) {
-            wave_lds_fence();
-#pragma unroll
-            for (int e = 0; e < 8; e++) xu[swz(lay(t, e, BK))] = v[e];
-            wave_lds_fence();
-#pragma unroll
-            for (int e = 0; e < 8; e++) v[e] = xu[swz(lay(t, e, B_A))];
         };
-        back(c0v);
-        back(c1v);
-#pragma unroll
-        for (int e = 0; e < 8; e++)
-        {
-            const u32 r = lay(t, e, B_A);
-            o0[r] = c0v[e];
-            o1[r] = c1v[e];
-        }
+        finish(std::integral_constant<int, 0>{});
+        if constexpr (NE == 2) finish(std::integral_constant<int, 1>{});
     };
     if constexpr (FP)
     {
@@ -1989,10 +2079,19 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8) ? MHE_KS_OCC : 2) vo
 
 // measured at L=44: G=1 763, 2 738, 4 700 HMult/s (digit groups with a partial-sum reduction, since
 // removed); ResNet-20 (L <= 31): G=1 0.865-0.873 images/s vs 0.832-0.839 with G=2
+// Pairing of the entries of a shared-key launch (k_ks_row_mac NE = 2): the context's switch
+// (MHE_KS_PAIR) and its counters of fused-MAC launches that ran paired / one entry per workgroup
+// (mhe_ks_pair_stats: a parity test of the paired kernel must see that it ran)
+struct KsPair
+{
+    int on;
+    std::atomic<unsigned long long> *paired, *single;
+};
+
 template <int LOGR, bool FP, bool MIX = false>
 static inline int ks_row_mac_a(const KsPtrs &P, int B, const PrimeDev *primes, const Tw *tw, int L, int K, int log_n,
-                               long long twd, int I0, int cnt, int pack, int kpack, int share, const Tw *itw,
-                               long long tinv, int inv_special, hipStream_t st)
+                               long long twd, int I0, int cnt, int pack, int kpack, int share, const KsPair &pr,
+                               const Tw *itw, long long tinv, int inv_special, hipStream_t st)
 {
     const int blocks = 1 << (log_n - LOGR);
     if constexpr (MIX)
@@ -2001,45 +2100,79 @@ static inline int ks_row_mac_a(const KsPtrs &P, int B, const PrimeDev *primes, c
         share = (share && B > 1 && (g.x * g.y) % 8 == 0) ? 1 : 0;
         hipLaunchKernelGGL((k_ks_row_mac<LOGR, true, true>), g, dim3(256), 0, st, P, primes, tw, L, K, log_n, twd,
                            I0, pack, kpack, share, itw, tinv, inv_special);
+        ++*pr.single;
         return inv_special;
     }
-    const dim3 grid(blocks / RowMacShape<LOGR>::S, cnt, B);
-    share = (share && B > 1 && (grid.x * grid.y) % 8 == 0) ? 1 : 0;
-    hipLaunchKernelGGL((k_ks_row_mac<LOGR, FP>), grid, dim3(256), 0, st, P, primes, tw, L, K, log_n, twd, I0,
+    int Bs = B; // entries left to the one-entry kernel
+    KsPtrs Ps = P;
+    if constexpr (FP && !MIX && LOGR == 8)
+    {
+        // Two entries per workgroup (NE = 2) when every entry reads the same key (`share` as the
+        // caller passes it: ks_shared_key) and none carries a run_if flag (the hoisted rotations'
+        // fallback keeps the one-entry kernel: a flag skips single entries).  An odd B runs its
+        // leading B - 1 entries paired and the last one through the one-entry kernel, on the same
+        // stream.
+        bool flags = false;
+        for (int e = 0; e < B; e++) flags = flags || P.run_if[e] != nullptr;
+        if (pr.on && log_n == 16 && share && B >= 2 && !flags)
+        {
+            const int Bn = B / 2;
+            const dim3 g(blocks / RowMacShape<LOGR>::S, cnt, Bn);
+            const int deal = (Bn > 1 && (g.x * g.y) % 8 == 0) ? 1 : 0; // the XCD dealing, over pairs
+            hipLaunchKernelGGL((k_ks_row_mac<LOGR, true, false, 2>), g, dim3(256), 0, st, P, primes, tw, L, K, log_n,
+                               twd, I0, pack, kpack, deal, itw, tinv, inv_special);
+            ++*pr.paired;
+            Bs = B - 2 * Bn;
+            if (Bs == 0) return inv_special;
+            const int e = B - 1; // the odd entry, as entry 0 of a launch of one
+            Ps.coeff[0] = P.coeff[e];
+            Ps.inter[0] = P.inter[e];
+            Ps.target[0] = P.target[e];
+            Ps.key[0] = P.key[e];
+            Ps.acc[0] = P.acc[e];
+            Ps.key_limbs[0] = P.key_limbs[e];
+            Ps.run_if[0] = nullptr;
+        }
+    }
+    const dim3 grid(blocks / RowMacShape<LOGR>::S, cnt, Bs);
+    share = (share && Bs > 1 && (grid.x * grid.y) % 8 == 0) ? 1 : 0;
+    hipLaunchKernelGGL((k_ks_row_mac<LOGR, FP>), grid, dim3(256), 0, st, Ps, primes, tw, L, K, log_n, twd, I0,
                        pack, kpack, share, itw, tinv, inv_special);
+    ++*pr.single;
     return inv_special;
 }
 
 template <int LOGR>
 static inline int ks_row_mac_m(const KsPtrs &P, int B, const PrimeDev *primes, const Tw *tw, int L, int K, int log_n,
-                               const NttMode &m, int I0, int cnt, int pack, int kpack, int share, const Tw *itw,
-                               int inv_special, hipStream_t st)
+                               const NttMode &m, int I0, int cnt, int pack, int kpack, int share, const KsPair &pr,
+                               const Tw *itw, int inv_special, hipStream_t st)
 {
     if (m.fp == 2)
-        return ks_row_mac_a<LOGR, true, true>(P, B, primes, tw, L, K, log_n, m.dfwd, I0, cnt, pack, kpack, share, itw,
+        return ks_row_mac_a<LOGR, true, true>(P, B, primes, tw, L, K, log_n, m.dfwd, I0, cnt, pack, kpack, share, pr, itw,
                                               m.dinv, inv_special, st);
     if (m.fp)
-        return ks_row_mac_a<LOGR, true>(P, B, primes, tw, L, K, log_n, m.dfwd, I0, cnt, pack, kpack, share, itw, m.dinv,
-                                        inv_special, st);
-    return ks_row_mac_a<LOGR, false>(P, B, primes, tw, L, K, log_n, 0, I0, cnt, pack, kpack, share, itw, 0, inv_special,
-                                     st);
+        return ks_row_mac_a<LOGR, true>(P, B, primes, tw, L, K, log_n, m.dfwd, I0, cnt, pack, kpack, share, pr, itw,
+                                        m.dinv, inv_special, st);
+    return ks_row_mac_a<LOGR, false>(P, B, primes, tw, L, K, log_n, 0, I0, cnt, pack, kpack, share, pr, itw, 0,
+                                     inv_special, st);
 }
 
 // Fused row pass + MAC for output primes I0 .. I0+cnt-1 (each entry's inter holds exactly those),
-// over B batch entries; share: every entry's key pointer is the same (XCD-grouped entries)
+// over B batch entries; share: every entry's key pointer is the same (XCD-grouped entries, and at
+// n = 2^16 in FP64 two entries per workgroup: pr, ks_row_mac_a)
 // inv_special: the launch covers the special prime (I = L) and may finish the special limbs' inverse
 // row pass itself (itw: inverse twiddles); returns 1 when it did, 0 when k_inv_row must still run.
 static inline int ks_row_mac_chunk(const KsPtrs &P, int B, const PrimeDev *primes, const Tw *tw, int L, int K,
                                    int log_n, const NttMode &m, int I0, int cnt, int pack, int kpack, int share,
-                                   const Tw *itw, int inv_special, hipStream_t st)
+                                   const KsPair &pr, const Tw *itw, int inv_special, hipStream_t st)
 {
     switch (log_n / 2)
     {
-    case 6: return ks_row_mac_m<6>(P, B, primes, tw, L, K, log_n, m, I0, cnt, 0, kpack, share, itw, inv_special, st);
-    case 7: return ks_row_mac_m<7>(P, B, primes, tw, L, K, log_n, m, I0, cnt, 0, kpack, share, itw, inv_special, st);
+    case 6: return ks_row_mac_m<6>(P, B, primes, tw, L, K, log_n, m, I0, cnt, 0, kpack, share, pr, itw, inv_special, st);
+    case 7: return ks_row_mac_m<7>(P, B, primes, tw, L, K, log_n, m, I0, cnt, 0, kpack, share, pr, itw, inv_special, st);
     case 8:
         return ks_row_mac_m<8>(P, B, primes, tw, L, K, log_n, m, I0, cnt, (pack && log_n == 16) ? 1 : 0, kpack, share,
-                               itw, inv_special, st);
+                               pr, itw, inv_special, st);
     }
     return 0;
 }

@@ -151,7 +151,7 @@ static int hoist_check_pass(mhe_ctx *c, const u64 *const *in, int count, const i
         for (int e = 0; e < B; e++)
             HIP_TRY(hipMemcpyAsync(fl + e, flags + ent_in[i0 + e], sizeof(int), hipMemcpyDeviceToDevice, st));
         if ((r = permute_batch(c, gp, B, L, st, false))) break;
-        if ((r = run_switch_key_batch(c, jobs, B, L, st, 1))) break;
+        if ((r = run_switch_key_batch(c, jobs, B, L, st, 1, nullptr, 0))) break; // the one-entry key MAC
         for (int e = 0; e < B; e++)
             hipLaunchKernelGGL(k_cmp_words, dim3((unsigned)((2 * ps + 255) / 256)), dim3(256), 0, st,
                                tmp + (size_t)e * 2 * ps, out[i0 + e], 2 * ps, cnt + 2 * e);
@@ -333,7 +333,7 @@ static int run_galois_hoisted(mhe_ctx *c, const u64 *const *in, int H, int count
         const KsPtrs kp = ks_ptrs(w, jobs, B, accs, flagged);
         modup_col(kp, B, c->primes, c->tw, L, c->K, log_n, c->nm_ks, 0, L + 1, IG, pack, st);
         ks_row_mac_chunk(kp, B, c->primes, c->tw, L, c->K, log_n, c->nm_ks, 0, L + 1, pack, kpack, ks_shared_key(c, jobs, B),
-                         c->itw, 0, st);
+                         ks_pair_of(c), c->itw, 0, st);
         HIP_LAUNCH_CHECK();
         run_moddown(c, jobs, B, L, w, 0, 1, st, accs);
     }
@@ -479,6 +479,14 @@ MHE_EXPORT int mhe_hoist_stats(mhe_ctx *c, uint64_t *rotations, uint64_t *mac_la
     *rotations = reset ? c->hoist_rot.exchange(0) : c->hoist_rot.load();
     *mac_launches = reset ? c->hoist_mac.exchange(0) : c->hoist_mac.load();
     *check_mismatches = reset ? c->hoist_bad.exchange(0) : c->hoist_bad.load();
+    return MHE_OK;
+}
+
+MHE_EXPORT int mhe_ks_pair_stats(mhe_ctx *c, uint64_t *paired, uint64_t *single, int reset)
+{
+    if (!valid_ctx(c) || !paired || !single) return fail(MHE_ERR_ARG, "invalid argument");
+    *paired = reset ? c->ks_paired.exchange(0) : c->ks_paired.load();
+    *single = reset ? c->ks_single.exchange(0) : c->ks_single.load();
     return MHE_OK;
 }
 

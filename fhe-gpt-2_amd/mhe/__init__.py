@@ -37,6 +37,7 @@ SIGNATURES = {
     "mhe_ctx_get_hoist": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "mhe_hoist_stats": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
                                        ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
+    "mhe_ks_pair_stats": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
     "mhe_debug_fail_alloc": (ctypes.c_int, [vp, ctypes.c_int]),
     "mhe_debug_fail_switch": (ctypes.c_int, [vp, ctypes.c_int]),
     "mhe_alloc_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
@@ -256,6 +257,12 @@ class Engine:
         r, m, b = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
         _check(lib().mhe_hoist_stats(self._h, ctypes.byref(r), ctypes.byref(m), ctypes.byref(b), 1 if reset else 0))
         return r.value, m.value, b.value
+
+    def ks_pair_stats(self, reset=False):
+        """(fused key-MAC launches that ran two entries per workgroup, launches that ran one)."""
+        p, s = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().mhe_ks_pair_stats(self._h, ctypes.byref(p), ctypes.byref(s), 1 if reset else 0))
+        return p.value, s.value
 
     @staticmethod
     def alloc_stats(reset=False):

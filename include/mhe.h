@@ -142,6 +142,11 @@ int mhe_kernel_time(mhe_ctx *ctx, int kernel, double *total_ms, int *launches);
 int mhe_ctx_set_hoist(mhe_ctx *ctx, int on, int check);
 int mhe_ctx_get_hoist(mhe_ctx *ctx, int *on, int *check);
 int mhe_hoist_stats(mhe_ctx *ctx, uint64_t *rotations, uint64_t *mac_launches, uint64_t *check_mismatches, int reset);
+/* Launches of the fused key-MAC kernel since the last reset: those that ran two batch entries per
+ * workgroup (n = 2^16, FP64 chains, every entry with the same key and no hoisting flag; MHE_KS_PAIR=0
+ * at context creation turns pairing off) and those that ran one.  A batch of an odd number of entries
+ * counts once in each. */
+int mhe_ks_pair_stats(mhe_ctx *ctx, uint64_t *paired, uint64_t *single, int reset);
 /* Device scratch the context holds: per-stream workspaces (key-switch / rescale scratch for up to
  * 8 batch entries at the key level, and the group accumulators of mhe_rotate_sum on the streams
  * that called it), hoisting buffers, Galois negation-mask tables, and the number of streams with a
