@@ -18,11 +18,14 @@
 // SEAL's "encoded values are too large" check needs max |coeff|: a host bound
 // (scale / n) * 2 * sum |v_i| settles it for every ordinary input; only when the bound comes
 // within a bit of the limit is the exact device maximum read back (one stream sync).
+// mhe_ckks_encode_dev runs the same steps for up to 8 vectors per launch that are already in device
+// memory (k_encb_*): no ring and no synchronisation, the size check decided on the device per entry.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <complex>
 #include <cstring>
+#include <limits>
 #include <mutex>
 #include <string>
 
@@ -33,6 +36,7 @@ extern "C" hipError_t mhe_internal_free(void *p, hipStream_t st);
 
 #include "../../include/mhe.h"
 #include "arith.h"
+#include "encode_check.h" // size_fits, l1_proves_size, largest_fitting
 
 typedef unsigned __int128 u128;
 typedef std::complex<double> cd;
@@ -40,6 +44,8 @@ typedef std::complex<double> cd;
 // shared with mhe.hip
 int mhe_internal_fail(int code, const char *msg);
 int mhe_internal_ntt_forward(mhe_ctx *c, uint64_t *data, int polys, int limbs, int full, hipStream_t st);
+int mhe_internal_ntt_forward_entries(mhe_ctx *c, uint64_t *const *data, int B, int limbs, const uint32_t *skip_if,
+                                     hipStream_t st);
 int mhe_internal_primes(mhe_ctx *c, const PrimeDev **dev, const uint64_t **host, int *count, int *log_n);
 
 struct mhe_encoder
@@ -60,7 +66,7 @@ struct mhe_encoder
     struct DevRoots
     {
         int dev;
-        double2 *roots; // inv_root_powers [n], then root_powers [n] (decode's forward FFT)
+        double2 *roots; // inv_root_powers [n], root_powers [n] (decode's forward FFT), inverse index map [n] u32
     };
     // decode's RNS constants of one level (the first `q.size()` primes of a chain) on one device:
     // Q, (Q+1)/2, (Q/q_j)^-1 mod q_j and the punctured products Q/q_j, W words each
@@ -148,8 +154,16 @@ u64 words_mod(const u64 *w, int nw, u64 q)
     return (u64)r;
 }
 
+int scale_fault(double scale, int bound_limbs, int tb)
+{
+    return mhe_internal_fail(MHE_ERR_ARG, ("scale out of bounds (encoding 2^" + std::to_string(std::log2(scale)) +
+                                           " at " + std::to_string(bound_limbs) + " limbs, " + std::to_string(tb) +
+                                           " bits)").c_str());
+}
+
 // The encoder's complex roots on device `dev`, uploaded once per device (caller holds e->mu):
-// inv_root_powers for encode's inverse FFT, root_powers behind them for decode's forward FFT.
+// inv_root_powers for encode's inverse FFT, root_powers behind them for decode's forward FFT, then
+// mhe_ckks_encode_dev's inverse index table (n 32-bit words, at roots + 2n).
 int device_roots(const mhe_encoder *e, int dev, const double2 **out)
 {
     for (auto &d : e->dev_roots)
@@ -159,11 +173,19 @@ int device_roots(const mhe_encoder *e, int dev, const double2 **out)
             return MHE_OK;
         }
     const size_t n = e->n;
+    // the inverse of index_map: position p of the FFT input holds slot w >> 1, conjugated when w & 1
+    std::vector<u32> inv(n);
+    for (size_t i = 0; i < e->slots; i++)
+    {
+        inv[e->index_map[i]] = (u32)(i << 1);
+        inv[e->index_map[e->slots | i]] = (u32)(i << 1) | 1;
+    }
     double2 *r = nullptr;
-    if (hipMalloc((void **)&r, 2 * n * sizeof(double2)) != hipSuccess)
+    if (hipMalloc((void **)&r, 2 * n * sizeof(double2) + n * sizeof(u32)) != hipSuccess)
         return mhe_internal_fail(MHE_ERR_MEMORY, "encoder roots allocation failed");
     if (hipMemcpy(r, e->inv_root_powers.data(), n * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(r + n, e->root_powers.data(), n * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess)
+        hipMemcpy(r + n, e->root_powers.data(), n * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(r + 2 * n, inv.data(), n * sizeof(u32), hipMemcpyHostToDevice) != hipSuccess)
     {
         (void)hipFree(r);
         return mhe_internal_fail(MHE_ERR_DEVICE, "encoder roots upload failed");
@@ -217,13 +239,12 @@ __device__ __forceinline__ void enc_bfly(double2 &x, double2 &y, double2 r, bool
 
 constexpr int kEncLogBlock = 12;
 
-// stages 0 .. lb-1 (gap 1 .. 2^(lb-1)) of one 2^lb-point block in LDS
-__global__ __launch_bounds__(256) void k_enc_fft_block(double2 *cv, const double2 *roots, int log_n, int lb,
-                                                       double scalar)
+// stages 0 .. lb-1 (gap 1 .. 2^(lb-1)) of the 2^lb-point block at `base`, held in LDS by a workgroup
+// of 256 lanes; barriers before the first and after every stage
+__device__ __forceinline__ void enc_block_stages(double2 *sh, const double2 *roots, size_t base, int log_n, int lb,
+                                                 double scalar)
 {
-    __shared__ double2 sh[1 << kEncLogBlock];
-    const size_t n = (size_t)1 << log_n, B = (size_t)1 << lb, base = (size_t)blockIdx.x << lb;
-    for (size_t t = threadIdx.x; t < B; t += 256) sh[t] = cv[base + t];
+    const size_t n = (size_t)1 << log_n, B = (size_t)1 << lb;
     __syncthreads();
     for (int st = 0; st < lb; st++)
     {
@@ -236,6 +257,15 @@ __global__ __launch_bounds__(256) void k_enc_fft_block(double2 *cv, const double
         }
         __syncthreads();
     }
+}
+
+__global__ __launch_bounds__(256) void k_enc_fft_block(double2 *cv, const double2 *roots, int log_n, int lb,
+                                                       double scalar)
+{
+    __shared__ double2 sh[1 << kEncLogBlock];
+    const size_t B = (size_t)1 << lb, base = (size_t)blockIdx.x << lb;
+    for (size_t t = threadIdx.x; t < B; t += 256) sh[t] = cv[base + t];
+    enc_block_stages(sh, roots, base, log_n, lb, scalar);
     for (size_t t = threadIdx.x; t < B; t += 256) cv[base + t] = sh[t];
 }
 
@@ -244,15 +274,11 @@ __global__ __launch_bounds__(256) void k_enc_fft_block(double2 *cv, const double
 // runs the stages in order -- the same butterflies on the same values as one k_enc_fft_stage launch
 // per stage, so the same doubles, in one launch instead of log_n - lb
 template <int LR> // log_n - lb
-__global__ __launch_bounds__(256) void k_enc_fft_tail(double2 *cv, const double2 *roots, int log_n, int lb,
-                                                      double scalar)
+__device__ __forceinline__ void enc_tail_stages(double2 (&v)[1 << LR], const double2 *roots, int log_n, int lb,
+                                                double scalar)
 {
     constexpr int R = 1 << LR;
-    const size_t n = (size_t)1 << log_n, c = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (c >= ((size_t)1 << lb)) return;
-    double2 v[R];
-#pragma unroll
-    for (int j = 0; j < R; j++) v[j] = cv[c + ((size_t)j << lb)];
+    const size_t n = (size_t)1 << log_n;
 #pragma unroll
     for (int s = 0; s < LR; s++)
     {
@@ -266,6 +292,19 @@ __global__ __launch_bounds__(256) void k_enc_fft_tail(double2 *cv, const double2
                 enc_bfly(v[j], v[j + (1 << s)], r, m == 1, scalar);
             }
     }
+}
+
+template <int LR>
+__global__ __launch_bounds__(256) void k_enc_fft_tail(double2 *cv, const double2 *roots, int log_n, int lb,
+                                                      double scalar)
+{
+    constexpr int R = 1 << LR;
+    const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= ((size_t)1 << lb)) return;
+    double2 v[R];
+#pragma unroll
+    for (int j = 0; j < R; j++) v[j] = cv[c + ((size_t)j << lb)];
+    enc_tail_stages<LR>(v, roots, log_n, lb, scalar);
 #pragma unroll
     for (int j = 0; j < R; j++) cv[c + ((size_t)j << lb)] = v[j];
 }
@@ -288,15 +327,10 @@ __global__ void k_enc_absmax(const double2 *cv, size_t n, unsigned long long *mx
     if ((threadIdx.x & 63) == 0) atomicMax(mx, v);
 }
 
-// out[j][i] = round(Re cv_i) mod q_j, sign applied (ckks.h:545-640)
-__global__ void k_enc_round_reduce(const double2 *cv, u64 *out, const PrimeDev *primes, int limbs, int log_n)
+// round(re) mod p.q, sign applied (ckks.h:545-640)
+__device__ __forceinline__ u64 enc_residue(double re, const PrimeDev &p)
 {
-    const size_t n = (size_t)1 << log_n;
-    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (g >= n * limbs) return;
-    const size_t i = g & (n - 1);
-    const PrimeDev p = primes[g >> log_n];
-    double c = round(cv[i].x);
+    double c = round(re);
     const bool neg = signbit(c);
     c = fabs(c);
     u64 r;
@@ -314,7 +348,115 @@ __global__ void k_enc_round_reduce(const double2 *cv, u64 *out, const PrimeDev *
         r = 0;
         for (int k = nw - 1; k >= 0; k--) r = barrett128(w[k], r, p);
     }
-    out[g] = (neg && r) ? p.q - r : r;
+    return (neg && r) ? p.q - r : r;
+}
+
+// out[j][i] = round(Re cv_i) mod q_j
+__global__ void k_enc_round_reduce(const double2 *cv, u64 *out, const PrimeDev *primes, int limbs, int log_n)
+{
+    const size_t n = (size_t)1 << log_n;
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= n * limbs) return;
+    out[g] = enc_residue(cv[g & (n - 1)].x, primes[g >> log_n]);
+}
+
+// ---- mhe_ckks_encode_dev: the same steps for up to MHE_MAXB entries per launch (entry =
+// blockIdx.y), the values read from device memory
+#ifndef MHE_MAXB
+#define MHE_MAXB 8 // as ntt.h
+#endif
+
+struct EncB
+{
+    const double *vals[MHE_MAXB]; // count reals or (re, im) pairs; may be null when count is 0
+    u64 *out[MHE_MAXB];           // [limbs][n]
+    u32 check;                    // bit b: entry b's maximum is taken and compared on the device
+};
+
+// the workgroup's part of max |Re cv_i| of one entry, as ordered bit patterns (k_enc_absmax); a NaN
+// orders above every finite value and above Inf.  Whole waves call this.
+__device__ __forceinline__ void enc_max_fold(unsigned long long v, unsigned long long *mx)
+{
+    for (int o = 32; o; o >>= 1) v = max(v, (unsigned long long)__shfl_xor(v, o));
+    if ((threadIdx.x & 63) == 0) atomicMax(mx, v);
+}
+__device__ __forceinline__ unsigned long long enc_abs_bits(double x)
+{
+    return (unsigned long long)__double_as_longlong(fabs(x));
+}
+
+// k_enc_scatter and k_enc_fft_block in one: position p of the block is read straight from the
+// entry's values through the inverse index table (slot w >> 1, conjugated when w & 1; a slot at or
+// past count is zero), so cv needs no memset and no scatter pass.  With lb == log_n this kernel runs
+// the last stage and folds the entry's maximum in.
+__global__ __launch_bounds__(256) void k_encb_fft_block(EncB P, size_t count, int is_complex, const u32 *inv_index,
+                                                        double2 *cv, const double2 *roots, int log_n, int lb,
+                                                        double scalar, unsigned long long *mx)
+{
+    __shared__ double2 sh[1 << kEncLogBlock];
+    const int b = blockIdx.y;
+    const size_t B = (size_t)1 << lb, base = (size_t)blockIdx.x << lb;
+    const double *vals = P.vals[b];
+    for (size_t t = threadIdx.x; t < B; t += 256)
+    {
+        const u32 w = inv_index[base + t];
+        const size_t slot = w >> 1;
+        double2 z = double2{ 0.0, 0.0 };
+        if (slot < count)
+        {
+            const double re = is_complex ? vals[2 * slot] : vals[slot], im = is_complex ? vals[2 * slot + 1] : 0.0;
+            z = double2{ re, (w & 1) ? -im : im };
+        }
+        sh[t] = z;
+    }
+    enc_block_stages(sh, roots, base, log_n, lb, scalar);
+    cv += (size_t)b << log_n;
+    for (size_t t = threadIdx.x; t < B; t += 256) cv[base + t] = sh[t];
+    if (lb == log_n && ((P.check >> b) & 1)) // uniform per workgroup
+    {
+        unsigned long long m = 0;
+        for (size_t t = threadIdx.x; t < B; t += 256) m = max(m, enc_abs_bits(sh[t].x));
+        enc_max_fold(m, mx + b);
+    }
+}
+
+// k_enc_fft_tail per entry; it always holds the last stage, so the entry's maximum is folded in
+template <int LR>
+__global__ __launch_bounds__(256) void k_encb_fft_tail(double2 *cv, const double2 *roots, int log_n, int lb,
+                                                       double scalar, u32 check, unsigned long long *mx)
+{
+    constexpr int R = 1 << LR;
+    const int b = blockIdx.y;
+    const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x; // 2^lb is a multiple of 256: no partial workgroup
+    cv += (size_t)b << log_n;
+    double2 v[R];
+#pragma unroll
+    for (int j = 0; j < R; j++) v[j] = cv[c + ((size_t)j << lb)];
+    enc_tail_stages<LR>(v, roots, log_n, lb, scalar);
+    unsigned long long m = 0;
+#pragma unroll
+    for (int j = 0; j < R; j++)
+    {
+        cv[c + ((size_t)j << lb)] = v[j];
+        m = max(m, enc_abs_bits(v[j].x));
+    }
+    if ((check >> b) & 1) enc_max_fold(m, mx + b);
+}
+
+// k_enc_round_reduce per entry.  A checked entry whose maximum is above max_ok (the bits of the
+// largest double SEAL's size check accepts) is rejected: status 1 and its output is left alone.
+// One lane writes the entry's status word (status may be null when no entry is checked).
+__global__ void k_encb_round_reduce(EncB P, const double2 *cv, const PrimeDev *primes, int limbs, int log_n,
+                                    const unsigned long long *mx, unsigned long long max_ok, u32 *status)
+{
+    const int b = blockIdx.y;
+    const bool rejected = ((P.check >> b) & 1) && mx[b] > max_ok;
+    if (status && blockIdx.x == 0 && threadIdx.x == 0) status[b] = rejected ? 1u : 0u;
+    if (rejected) return;
+    const size_t n = (size_t)1 << log_n;
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= n * limbs) return;
+    P.out[b][g] = enc_residue(cv[((size_t)b << log_n) + (g & (n - 1))].x, primes[g >> log_n]);
 }
 } // namespace
 
@@ -368,10 +510,7 @@ extern "C" __attribute__((visibility("default"))) int mhe_ckks_encode_at(mhe_ctx
     if (limbs < 1 || limbs > bound_limbs || bound_limbs > K || !out)
         return mhe_internal_fail(MHE_ERR_ARG, "parms_id is not valid for encryption parameters");
     const int tb = total_bits(q, bound_limbs);
-    if (scale <= 0 || (static_cast<int>(std::log2(scale)) + 1 >= tb))
-        return mhe_internal_fail(MHE_ERR_ARG, ("scale out of bounds (encoding 2^" + std::to_string(std::log2(scale)) +
-                                               " at " + std::to_string(bound_limbs) + " limbs, " + std::to_string(tb) +
-                                               " bits)").c_str());
+    if (scale <= 0 || (static_cast<int>(std::log2(scale)) + 1 >= tb)) return scale_fault(scale, bound_limbs, tb);
     const size_t n = e->n;
     hipStream_t st = (hipStream_t)stream;
     int dev = 0;
@@ -381,9 +520,7 @@ extern "C" __attribute__((visibility("default"))) int mhe_ckks_encode_at(mhe_ctx
     double l1 = 0;
     for (size_t i = 0; i < count; i++) l1 += std::fabs(re[i]) + (im ? std::fabs(im[i]) : 0.0);
     const double fix = scale / static_cast<double>(n);
-    const double bound = fix * 2 * l1 * (1 + 1e-6) + 1;
-    const bool exact_check = !(std::isfinite(bound) &&
-                               static_cast<int>(std::ceil(std::log2(std::max<double>(bound, 1.0)))) + 1 < tb);
+    const bool exact_check = !l1_proves_size(fix, l1, tb);
 
     std::unique_lock<std::mutex> lk(e->mu);
     const double2 *roots = nullptr;
@@ -471,8 +608,7 @@ extern "C" __attribute__((visibility("default"))) int mhe_ckks_encode_at(mhe_ctx
         {
             double max_coeff;
             std::memcpy(&max_coeff, &h_mx, sizeof(double));
-            const int max_bits = static_cast<int>(std::ceil(std::log2(std::max<double>(max_coeff, 1.0)))) + 1;
-            if (!(max_bits < tb)) // NaN compares false: rejected as well
+            if (!size_fits(max_coeff, tb))
             {
                 (void)mhe_internal_free(buf, st);
                 return mhe_internal_fail(MHE_ERR_ARG, "encoded values are too large");
@@ -497,6 +633,133 @@ extern "C" __attribute__((visibility("default"))) int mhe_ckks_encode(mhe_ctx *c
                                                                      uint64_t *out, void *stream)
 {
     return mhe_ckks_encode_at(c, e, re, im, count, scale, limbs, limbs, out, stream);
+}
+
+// 1 when mhe_ckks_encode_dev encodes an entry with this l1 bound unchecked, else 0 (host only)
+extern "C" __attribute__((visibility("default"))) int mhe_ckks_encode_l1_proves(mhe_ctx *c, double scale,
+                                                                               int bound_limbs, double l1)
+{
+    const PrimeDev *primes;
+    const uint64_t *q;
+    int K, log_n;
+    if (mhe_internal_primes(c, &primes, &q, &K, &log_n)) return mhe_internal_fail(MHE_ERR_ARG, "context is not valid");
+    if (bound_limbs < 1 || bound_limbs > K)
+        return mhe_internal_fail(MHE_ERR_ARG, "parms_id is not valid for encryption parameters");
+    const double fix = scale / static_cast<double>((size_t)1 << log_n);
+    return l1 >= 0 && l1_proves_size(fix, l1, total_bits(q, bound_limbs)) ? 1 : 0;
+}
+
+// CKKSEncoder::encode of `entries` vectors that are already in device memory, MHE_MAXB per round:
+// per round one memset of the maxima (when an entry is checked), k_encb_fft_block, k_encb_fft_tail,
+// k_encb_round_reduce and the two NTT passes.  Stream-ordered: nothing here waits for the device.
+extern "C" __attribute__((visibility("default"))) int mhe_ckks_encode_dev(
+    mhe_ctx *c, const mhe_encoder *e, int entries, const double *const *values_dev, size_t count, int is_complex,
+    double scale, int bound_limbs, int limbs, uint64_t *const *out_dev, const double *l1_bounds, uint32_t *status_dev,
+    void *stream)
+{
+    const PrimeDev *primes;
+    const uint64_t *q;
+    int K, log_n;
+    if (mhe_internal_primes(c, &primes, &q, &K, &log_n)) return mhe_internal_fail(MHE_ERR_ARG, "context is not valid");
+    if (!e || e->log_n != log_n) return mhe_internal_fail(MHE_ERR_ARG, "encoder does not match the context");
+    // the widest register tail is k_encb_fft_tail<4> (no context has a larger ring)
+    if (log_n > kEncLogBlock + 4) return mhe_internal_fail(MHE_ERR_ARG, "poly_modulus_degree is invalid");
+    if (entries < 1) return mhe_internal_fail(MHE_ERR_ARG, "entries must be at least 1");
+    if (count > 0 && !values_dev) return mhe_internal_fail(MHE_ERR_ARG, "values cannot be null");
+    for (int b = 0; b < entries && count > 0; b++)
+        if (!values_dev[b]) return mhe_internal_fail(MHE_ERR_ARG, "values cannot be null");
+    if (count > e->slots) return mhe_internal_fail(MHE_ERR_ARG, "values_size is too large");
+    if (limbs < 1 || limbs > bound_limbs || bound_limbs > K || !out_dev)
+        return mhe_internal_fail(MHE_ERR_ARG, "parms_id is not valid for encryption parameters");
+    for (int b = 0; b < entries; b++)
+        if (!out_dev[b]) return mhe_internal_fail(MHE_ERR_ARG, "parms_id is not valid for encryption parameters");
+    const int tb = total_bits(q, bound_limbs);
+    if (scale <= 0 || (static_cast<int>(std::log2(scale)) + 1 >= tb)) return scale_fault(scale, bound_limbs, tb);
+    const size_t n = e->n;
+    // every entry of a round runs inside the same launches: an output may share no byte with another
+    // output or with any entry's values
+    const size_t ob = (size_t)limbs * n * sizeof(u64), vb = count * (is_complex ? 2 : 1) * sizeof(double);
+    for (int i = 0; i < entries; i++)
+    {
+        const char *o = (const char *)out_dev[i];
+        for (int j = 0; j < entries; j++)
+        {
+            const char *o2 = (const char *)out_dev[j], *v = count ? (const char *)values_dev[j] : nullptr;
+            if ((j != i && o < o2 + ob && o2 < o + ob) || (vb && o < v + vb && v < o + ob))
+                return mhe_internal_fail(MHE_ERR_ARG, "encode output must not alias another output or an input");
+        }
+    }
+    // entries whose l1 bound does not prove SEAL's size check are checked on the device
+    const double fix = scale / static_cast<double>(n);
+    std::vector<char> checked(entries);
+    bool any_checked = false;
+    for (int b = 0; b < entries; b++)
+    {
+        const bool known = l1_bounds && l1_bounds[b] >= 0; // false for NaN
+        checked[b] = !(known && l1_proves_size(fix, l1_bounds[b], tb)); // mhe_ckks_encode_l1_proves
+        any_checked |= checked[b] != 0;
+    }
+    if (any_checked && !status_dev)
+        return mhe_internal_fail(MHE_ERR_ARG, "status_dev cannot be null when an entry needs the device size check");
+    unsigned long long max_ok = 0;
+    if (any_checked)
+    {
+        const double m = largest_fitting(tb);
+        std::memcpy(&max_ok, &m, sizeof m);
+    }
+
+    hipStream_t st = (hipStream_t)stream;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return mhe_internal_fail(MHE_ERR_DEVICE, "no device");
+    const double2 *roots = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(e->mu);
+        if (int rc = device_roots(e, dev, &roots)) return rc;
+    }
+    const u32 *inv_index = (const u32 *)(roots + 2 * n);
+    // staging: [cv: n double2 per entry of a round][max words]; the rounds follow each other on st
+    const int R = std::min(entries, MHE_MAXB);
+    char *buf = nullptr;
+    if (mhe_internal_alloc((void **)&buf, (size_t)R * n * sizeof(double2) + MHE_MAXB * sizeof(u64), st) != hipSuccess)
+        return mhe_internal_fail(MHE_ERR_MEMORY, "encode staging allocation failed");
+    double2 *cv = (double2 *)buf;
+    unsigned long long *mx = (unsigned long long *)(cv + (size_t)R * n);
+    const int lb = std::min(log_n, kEncLogBlock);
+    const dim3 block(256);
+    hipError_t err = hipSuccess;
+    int rc = MHE_OK;
+    for (int i0 = 0; i0 < entries && err == hipSuccess && rc == MHE_OK; i0 += MHE_MAXB)
+    {
+        const int B = std::min(MHE_MAXB, entries - i0);
+        EncB P{};
+        for (int b = 0; b < B; b++)
+        {
+            P.vals[b] = count ? values_dev[i0 + b] : nullptr;
+            P.out[b] = out_dev[i0 + b];
+            if (checked[i0 + b]) P.check |= 1u << b;
+        }
+        if (P.check && (err = hipMemsetAsync(mx, 0, MHE_MAXB * sizeof(u64), st)) != hipSuccess) break;
+        hipLaunchKernelGGL(k_encb_fft_block, dim3((unsigned)(n >> lb), (unsigned)B), block, 0, st, P, count,
+                           is_complex ? 1 : 0, inv_index, cv, roots, log_n, lb, fix, mx);
+        const dim3 tg((unsigned)(((size_t)1 << lb) / 256), (unsigned)B);
+        switch (log_n - lb)
+        {
+        case 0: break;
+        case 1: hipLaunchKernelGGL(k_encb_fft_tail<1>, tg, block, 0, st, cv, roots, log_n, lb, fix, P.check, mx); break;
+        case 2: hipLaunchKernelGGL(k_encb_fft_tail<2>, tg, block, 0, st, cv, roots, log_n, lb, fix, P.check, mx); break;
+        case 3: hipLaunchKernelGGL(k_encb_fft_tail<3>, tg, block, 0, st, cv, roots, log_n, lb, fix, P.check, mx); break;
+        default: hipLaunchKernelGGL(k_encb_fft_tail<4>, tg, block, 0, st, cv, roots, log_n, lb, fix, P.check, mx); break;
+        }
+        u32 *status = status_dev ? status_dev + i0 : nullptr;
+        hipLaunchKernelGGL(k_encb_round_reduce, dim3((unsigned)((n * limbs + 255) / 256), (unsigned)B), block, 0, st, P,
+                           cv, primes, limbs, log_n, mx, max_ok, status);
+        err = hipGetLastError();
+        if (err == hipSuccess) rc = mhe_internal_ntt_forward_entries(c, P.out, B, limbs, P.check ? status : nullptr, st);
+    }
+    (void)mhe_internal_free(buf, st);
+    if (rc != MHE_OK) return rc;
+    if (err != hipSuccess) return mhe_internal_fail(MHE_ERR_DEVICE, hipGetErrorString(err));
+    return MHE_OK;
 }
 
 extern "C" __attribute__((visibility("default"))) int mhe_ckks_encode_scalar_at(mhe_ctx *c, double value, double scale,

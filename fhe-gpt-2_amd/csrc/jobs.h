@@ -60,6 +60,19 @@ struct JobFwdPlain : JobPlain
     __device__ V2 view(int y) const { return V2{ JobPlain::view(y) }; }
 };
 
+// The forward transform of a batch entry that a kernel earlier in the stream may have rejected
+// (mhe_ckks_encode_dev): every job returns when *skip_if != 0; null: always runs.
+struct JobFwdPlainIf : JobFwdPlain
+{
+    const u32 *skip_if;
+    __device__ V2 view(int y) const
+    {
+        V2 v = JobFwdPlain::view(y);
+        v.skip = skip_if && *skip_if;
+        return v;
+    }
+};
+
 struct JobInvPlain : JobPlain
 {
     struct V2 : View

@@ -724,6 +724,27 @@ int mhe_internal_ntt_forward(mhe_ctx *c, uint64_t *data, int polys, int limbs, i
     return run_ntt_fwd(c, data, data, polys, limbs, full, st);
 }
 
+// Full forward NTT in place of B <= MHE_MAXB plaintexts [limbs][n] in one pair of launches; entry
+// e's workgroups return when the device word skip_if[e] is nonzero (skip_if null: all run).
+int mhe_internal_ntt_forward_entries(mhe_ctx *c, uint64_t *const *data, int B, int limbs, const uint32_t *skip_if,
+                                     hipStream_t st)
+{
+    if (B < 1 || B > MHE_MAXB) return fail(MHE_ERR_ARG, "forward NTT: batch size out of range");
+    count_op(c, MHE_OPK_NTT, limbs, (unsigned long long)B);
+    JobB<JobFwdPlainIf> col, row;
+    col.per = row.per = limbs;
+    for (int e = 0; e < B; e++)
+    {
+        const u32 *flag = skip_if ? skip_if + e : nullptr;
+        col.j[e] = JobFwdPlainIf{ fwd_plain(c, data[e], data[e], limbs, 0), flag };
+        row.j[e] = JobFwdPlainIf{ fwd_plain(c, data[e], data[e], limbs, 1), flag };
+    }
+    fwd_col(col, c->log_n, B * limbs, c->nm, st);
+    fwd_row(row, c->log_n, B * limbs, c->nm, st);
+    HIP_LAUNCH_CHECK();
+    return MHE_OK;
+}
+
 int mhe_internal_primes(mhe_ctx *c, const PrimeDev **dev, const uint64_t **host, int *count, int *log_n)
 {
     if (!valid_ctx(c)) return MHE_ERR_ARG;

@@ -675,12 +675,25 @@ public:
                 MemoryPoolHandle = {});
     void encode(double value, parms_id_type parms_id, double scale, Plaintext &destination, MemoryPoolHandle = {});
     void encode(double value, double scale, Plaintext &destination, MemoryPoolHandle = {});
+    // (not SEAL API) encode(*values[i], parms_id, scale, *destinations[i]) for every i, the vectors
+    // all of one size: one upload and one batched device encode (mhe_ckks_encode_dev) instead of a
+    // launch sequence per vector; the words, scale and parms_id of the single calls.  Throws as
+    // encode does; when a call throws ("encoded values are too large" for one vector, say) no
+    // destination has changed.  With set_batched_launches(false) or under MHE_EVAL_TRACE it calls
+    // encode per entry, into fresh plaintexts as well.  It synchronises the calling thread's stream
+    // once (after the upload, or with the status download when a vector needs the device check).
+    void encode_many(const std::vector<const std::vector<double> *> &values, parms_id_type parms_id, double scale,
+                     const std::vector<Plaintext *> &destinations);
+    void encode_many(const std::vector<const std::vector<std::complex<double>> *> &values, parms_id_type parms_id,
+                     double scale, const std::vector<Plaintext *> &destinations);
     void decode(const Plaintext &plain, std::vector<double> &destination, MemoryPoolHandle = {});
     void decode(const Plaintext &plain, std::vector<std::complex<double>> &destination, MemoryPoolHandle = {});
 
 private:
     void encode_internal(const double *re, const double *im, std::size_t count, parms_id_type parms_id,
                          double scale, Plaintext &destination);
+    void encode_many_internal(const std::vector<const double *> &data, std::size_t count, bool is_complex,
+                              parms_id_type parms_id, double scale, const std::vector<Plaintext *> &destinations);
     void decode_internal(const Plaintext &plain, std::vector<std::complex<double>> &out);
     SEALContext ctx_;
     mhe_encoder *enc_ = nullptr;

@@ -104,6 +104,9 @@ SIGNATURES = {
     "mhe_ckks_encode_scalar": (ctypes.c_int, [vp, ctypes.c_double, ctypes.c_double, ctypes.c_int, u64p]),
     "mhe_ckks_encode_at": (ctypes.c_int, [vp, vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                           ctypes.c_size_t, ctypes.c_double, ctypes.c_int, ctypes.c_int, vp, vp]),
+    "mhe_ckks_encode_dev": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_double,
+                                           ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]),
+    "mhe_ckks_encode_l1_proves": (ctypes.c_int, [vp, ctypes.c_double, ctypes.c_int, ctypes.c_double]),
     "mhe_ckks_decode": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.c_double, ctypes.c_size_t,
                                        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), vp]),
     "mhe_ckks_decode_dev": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.c_double, ctypes.c_size_t, vp, vp]),
@@ -568,6 +571,43 @@ class Engine:
                                         limbs if bound_limbs is None else bound_limbs, limbs, _ptr(out),
                                         self.stream()))
         return out
+
+    def encode_dev(self, values, scale, limbs, out=None, bound_limbs=None, l1_bounds=None, status=None):
+        """mhe_ckks_encode_dev: CKKSEncoder::encode of vectors that are already on the device, several
+        per launch.  `values`: a contiguous float64 or complex128 device tensor [count] or [B, count],
+        or a list of B such tensors of one shape.  Returns (out, status): out [B, limbs, n] as
+        Engine.empty makes it (or the given `out`), status an int32 device tensor [B] (0 = encoded,
+        1 = encoded values are too large, that entry of out untouched).  `l1_bounds`: per entry an
+        upper bound on sum |re| + |im| (negative or None: unknown, the entry is checked on the
+        device).  `status`: a tensor to reuse, or False to pass none (every bound must then suffice;
+        None is returned for it).  Enqueued on the current stream; never synchronises."""
+        torch = _torch()
+        vs = list(values) if isinstance(values, (list, tuple)) else \
+            [values] if values.dim() == 1 else [values[b] for b in range(values.shape[0])]
+        B = len(vs)
+        if B < 1:
+            raise ValueError("encode_dev needs at least one vector")
+        for v in vs:
+            if v.dtype not in (torch.float64, torch.complex128) or v.dtype != vs[0].dtype or v.dim() != 1 \
+                    or v.shape != vs[0].shape or not v.is_contiguous() or not v.is_cuda:
+                raise ValueError("values must be contiguous float64 or complex128 device vectors of one shape")
+        out = self.empty(B, limbs, self.n) if out is None else out
+        if out.dtype != torch.int64 or out.numel() != B * limbs * self.n or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError("out must be a contiguous int64 device tensor [B, limbs, n]")
+        if status is None:
+            status = torch.empty(B, dtype=torch.int32, device=self.torch_device)
+        elif status is False:
+            status = None
+        elif status.dtype != torch.int32 or status.numel() != B or not status.is_contiguous() or not status.is_cuda:
+            raise ValueError("status must be a contiguous int32 device tensor [B]")
+        stride = limbs * self.n * 8
+        outs = (ctypes.c_void_p * B)(*[out.data_ptr() + b * stride for b in range(B)])
+        l1 = None if l1_bounds is None else (ctypes.c_double * B)(*[-1.0 if x is None else float(x) for x in l1_bounds])
+        _check(lib().mhe_ckks_encode_dev(self._h, self._encoder(), B, self._ptrs(vs), vs[0].numel(),
+                                         1 if vs[0].dtype == torch.complex128 else 0, scale,
+                                         limbs if bound_limbs is None else bound_limbs, limbs, outs, l1,
+                                         None if status is None else _ptr(status), self.stream()))
+        return out, status
 
     def _encoder(self):
         if getattr(self, "_enc", None) is None:

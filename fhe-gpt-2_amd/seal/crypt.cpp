@@ -59,6 +59,133 @@ void CKKSEncoder::encode(const std::vector<std::complex<double>> &values, parms_
     encode_internal(re.data(), im.data(), values.size(), parms_id, scale, destination);
 }
 
+// data[b]: `count` reals, or with is_complex `count` (re, im) pairs, of entry b
+void CKKSEncoder::encode_many_internal(const std::vector<const double *> &data, std::size_t count, bool is_complex,
+                                       parms_id_type parms_id, double scale,
+                                       const std::vector<Plaintext *> &destinations)
+{
+    auto cd = ctx_.get_context_data(parms_id);
+    if (!cd) throw std::invalid_argument("parms_id is not valid for encryption parameters");
+    const std::size_t L = cd->parms().coeff_modulus().size(), B = data.size(), per = count * (is_complex ? 2 : 1);
+    if (count > slots_) throw std::invalid_argument("values_size is too large");
+    mhe_ctx *eng = ctx_.engine();
+    void *s = ctx_.stream();
+    // one upload of all the values; the host's l1 norms settle the size check of ordinary inputs, and
+    // the status words are read back only when some bound does not prove it
+    std::vector<double> host(B * per), l1(B, 0.0);
+    for (std::size_t b = 0; b < B; b++)
+        for (std::size_t i = 0; i < per; i++) l1[b] += std::fabs(host[b * per + i] = data[b][i]);
+    bool checked = false;
+    for (std::size_t b = 0; b < B && !checked; b++)
+        checked = mhe_ckks_encode_l1_proves(eng, scale, (int)L, l1[b]) != 1;
+    DevBuf staging(eng, s, host.size() + (B + 1) / 2);
+    double *vals = reinterpret_cast<double *>(staging.p);
+    auto *status = reinterpret_cast<std::uint32_t *>(vals + host.size());
+    // `host` is temporary: the stream is synchronised once before it goes -- right after the upload
+    // (ahead of the encode) when no status is read, else with the status download at the end; the
+    // guard covers a throw in between
+    struct SyncAtExit
+    {
+        mhe_ctx *eng;
+        void *s;
+        bool armed = false;
+        ~SyncAtExit()
+        {
+            if (armed) (void)mhe_stream_sync(eng, s);
+        }
+    } pending{ eng, s };
+    if (!host.empty())
+    {
+        chk(mhe_memcpy_h2d(eng, vals, host.data(), host.size() * sizeof(double), s));
+        pending.armed = true;
+        if (!checked)
+        {
+            pending.armed = false;
+            chk(mhe_stream_sync(eng, s));
+        }
+    }
+    // fresh plaintexts: the destinations change only when every entry has been accepted
+    std::vector<Plaintext> fresh(B);
+    std::vector<const double *> in(B);
+    std::vector<std::uint64_t *> out(B);
+    for (std::size_t b = 0; b < B; b++)
+    {
+        fresh[b].set_level(ctx_, parms_id, L);
+        fresh[b].scale() = scale;
+        in[b] = vals + b * per;
+        out[b] = fresh[b].store().dev_write(s, true);
+    }
+    chk(mhe_ckks_encode_dev(eng, enc_, (int)B, in.data(), count, is_complex ? 1 : 0, scale, (int)L, (int)L, out.data(),
+                            l1.data(), status, s));
+    if (checked)
+    {
+        std::vector<std::uint32_t> st(B);
+        chk(mhe_memcpy_d2h(eng, st.data(), status, B * sizeof(std::uint32_t), s));
+        pending.armed = false;
+        chk(mhe_stream_sync(eng, s));
+        for (std::uint32_t w : st)
+            if (w) throw std::invalid_argument("encoded values are too large");
+    }
+    for (std::size_t b = 0; b < B; b++) *destinations[b] = std::move(fresh[b]);
+}
+
+// encode_many one entry at a time (batched launches off, or a trace that keeps one record per
+// entry), also into fresh plaintexts: a throwing entry leaves every destination as it was
+template <class V>
+static void encode_each(CKKSEncoder &encoder, const std::vector<const V *> &values, parms_id_type parms_id,
+                        double scale, const std::vector<Plaintext *> &destinations)
+{
+    std::vector<Plaintext> fresh(values.size());
+    for (std::size_t i = 0; i < values.size(); i++) encoder.encode(*values[i], parms_id, scale, fresh[i]);
+    for (std::size_t i = 0; i < values.size(); i++) *destinations[i] = std::move(fresh[i]);
+}
+
+template <class V>
+static std::size_t check_many(const std::vector<const V *> &values, const std::vector<Plaintext *> &destinations)
+{
+    if (values.size() != destinations.size())
+        throw std::invalid_argument("values and destinations differ in number");
+    for (std::size_t i = 0; i < values.size(); i++)
+    {
+        if (!values[i] || !destinations[i]) throw std::invalid_argument("values and destinations cannot be null");
+        if (values[i]->size() != values[0]->size()) throw std::invalid_argument("values must have one size");
+        for (std::size_t j = 0; j < i; j++)
+            if (destinations[j] == destinations[i]) throw std::invalid_argument("destinations must be distinct");
+    }
+    return values.empty() ? 0 : values[0]->size();
+}
+
+void CKKSEncoder::encode_many(const std::vector<const std::vector<double> *> &values, parms_id_type parms_id,
+                              double scale, const std::vector<Plaintext *> &destinations)
+{
+    const std::size_t count = check_many(values, destinations);
+    if (!batched_launches() || trace::enabled())
+    {
+        encode_each(*this, values, parms_id, scale, destinations);
+        return;
+    }
+    if (values.empty()) return;
+    std::vector<const double *> data(values.size());
+    for (std::size_t i = 0; i < values.size(); i++) data[i] = values[i]->data();
+    encode_many_internal(data, count, false, parms_id, scale, destinations);
+}
+
+void CKKSEncoder::encode_many(const std::vector<const std::vector<std::complex<double>> *> &values,
+                              parms_id_type parms_id, double scale, const std::vector<Plaintext *> &destinations)
+{
+    const std::size_t count = check_many(values, destinations);
+    if (!batched_launches() || trace::enabled())
+    {
+        encode_each(*this, values, parms_id, scale, destinations);
+        return;
+    }
+    if (values.empty()) return;
+    // complex<double> is laid out as (re, im): the interleaved pairs the engine reads
+    std::vector<const double *> data(values.size());
+    for (std::size_t i = 0; i < values.size(); i++) data[i] = reinterpret_cast<const double *>(values[i]->data());
+    encode_many_internal(data, count, true, parms_id, scale, destinations);
+}
+
 void CKKSEncoder::encode(const std::vector<double> &values, double scale, Plaintext &destination, MemoryPoolHandle)
 {
     encode(values, ctx_.first_parms_id(), scale, destination);

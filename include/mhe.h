@@ -356,6 +356,34 @@ int mhe_ckks_encode_scalar(mhe_ctx *ctx, double value, double scale, int limbs, 
  * multiply_vector do, evaluator.cpp:287-310) without computing the dropped limbs. */
 int mhe_ckks_encode_at(mhe_ctx *ctx, const mhe_encoder *enc, const double *re, const double *im, size_t count,
                        double scale, int bound_limbs, int limbs, uint64_t *out_dev, void *stream);
+/* CKKSEncoder::encode of `entries` >= 1 vectors of one shape that are already in device memory,
+ * several per launch (rounds of 8): values_dev and out_dev are host arrays of `entries` device
+ * pointers.  Entry b reads `count` <= n/2 values -- real doubles, or with is_complex interleaved
+ * (re, im) pairs (what mhe_ckks_decode_dev writes) -- and writes the NTT-form plaintext [limbs][n],
+ * the words of mhe_ckks_encode_at(scale, bound_limbs, limbs), to out_dev[b].  count = 0 encodes the
+ * zero vector (the value pointers may then be null).  Stream-ordered: no host synchronisation, no
+ * pinned memory, staging from the caching allocator; the inputs are not written.
+ *
+ * Errors that do not depend on the values (the messages of mhe_ckks_encode_at; an output that
+ * overlaps another output or any entry's values) are returned before anything is launched and touch
+ * no output and no status word.  SEAL's size check (ckks.h:525-540) is settled per entry:
+ *   - l1_bounds (host array, may be NULL) gives an upper bound l1_bounds[b] >= 0 on
+ *     sum |re| + |im| of entry b; when the bound mhe_ckks_encode_at computes from it proves the
+ *     check, the entry is encoded unchecked (status 0);
+ *   - any other entry (NULL array, negative or NaN bound, bound not sufficient) is checked on the
+ *     device: its exact max |coefficient| is compared with the largest double the host's
+ *     expression accepts, so every finite maximum gets the host entry's verdict.  A maximum that is
+ *     Inf or NaN is always rejected (SEAL's expression is undefined there).
+ * status_dev (device, `entries` words; may be NULL only when no entry needs the device check) gets
+ * one word per entry: 0 = encoded, 1 = "encoded values are too large", and then out_dev[b] is
+ * left as it was. */
+int mhe_ckks_encode_dev(mhe_ctx *ctx, const mhe_encoder *enc, int entries, const double *const *values_dev,
+                        size_t count, int is_complex, double scale, int bound_limbs, int limbs,
+                        uint64_t *const *out_dev, const double *l1_bounds, uint32_t *status_dev, void *stream);
+/* Host only: 1 when the bound l1 proves the size check at (scale, bound_limbs), so that
+ * mhe_ckks_encode_dev encodes such an entry unchecked and its status word need not be read; 0 when
+ * the entry is checked on the device; negative (MHE_ERR_ARG) for an invalid context or level. */
+int mhe_ckks_encode_l1_proves(mhe_ctx *ctx, double scale, int bound_limbs, double l1);
 /* CKKSEncoder::decode (ckks.h:644-761): NTT-form plaintext [limbs][n] on the device ->
  * `sparse_slots` slot values (0 = n/2; the modified SEAL's sparse decode, ckks.h:704-713).
  * `im` may be NULL (decode to vector<double>).  Synchronous on `stream`: mhe_ckks_decode_dev
