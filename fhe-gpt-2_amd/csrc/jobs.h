@@ -551,6 +551,72 @@ struct JobMDRRow
     }
 };
 
+// The column pass of a summed HMult tail (mhe_relin_sum_rescale, prodsum.h): JobMDRCol with the
+// ModDown lift already taken and summed.  T[k][i] is the sum over a group's terms of the lifted
+// special limbs, canonical mod q_i (never summed mod P), so u_i = T_i P^-1 + r_i with r_i the rescale
+// lift of last = INTT(S[k][L-1]) exactly as JobMDRCol::View::load lifts it.  Job y = k*(L-1) + i;
+// JobMDRRow forms out_i from u_i, acc = A (the summed key products) and ct = C (the summed products).
+struct JobProdSumCol
+{
+    const u64 *T;    // [2][L][n], coefficient form, canonical mod q_i
+    const u64 *last; // [2][n] = INTT(S[k][L-1]), canonical
+    u64 *scratch;    // [2][L-1][n]
+    const PrimeDev *primes;
+    const Tw *tw;
+    const Tw *invq; // [K][K]
+    int L, K, log_n;
+    int fp = 0; // every prime < 2^51 (NttMode::fp): the lift in exact FP64 (fparith.h)
+    struct View
+    {
+        const u64 *Tp, *lastp;
+        u64 *dst;
+        PrimeDev p;
+        const Tw *tw;
+        Tw pinv;
+        u64 ql, halfL, neg_halfL;
+        bool redL, skip, fp;
+        double pd, pi, pinvd;
+        __device__ u64 load(u32 x) const
+        {
+            if (fp)
+            {
+                // T canonical and the rescale lift r + neg_halfL are exact doubles (< 2^52), the
+                // product by P^-1 is in (-1.25p, 1.25p), the sum below 2^53: one canonicalisation
+                const u64 r = csub(lastp[x] + halfL, ql);
+                const double u = fp_mulmod_gen(fp_from_u52(Tp[x]), pinvd, pd, pi) + fp_from_u52(r + neg_halfL);
+                return fp_canon(u, pd, pi);
+            }
+            u64 r = csub(lastp[x] + halfL, ql);
+            if (redL) r = barrett64(r, p);
+            r += neg_halfL;                                          // rescale lift, [0, 2q)
+            const u64 u = mul_shoup(Tp[x], pinv.x, pinv.y, p.q) + r; // [0, 3q)
+            return csub(csub(u, p.two_q), p.q);
+        }
+        __device__ void store(u32 x, u64 v) const { dst[x] = v; }
+    };
+    __device__ View view(int y) const
+    {
+        const int k = y / (L - 1), i = y % (L - 1);
+        View v;
+        v.Tp = T + ((size_t)(k * L + i) << log_n);
+        v.lastp = last + ((size_t)k << log_n);
+        v.dst = scratch + ((size_t)y << log_n);
+        v.p = prime_at(primes, i);
+        v.tw = tw + ((size_t)i << log_n);
+        v.pinv = tw_at(invq, (size_t)(K - 1) * K + i);
+        v.ql = prime_at(primes, L - 1).q;
+        v.halfL = v.ql >> 1;
+        v.neg_halfL = v.p.q - barrett64(v.halfL, v.p);
+        v.redL = v.p.q < v.ql;
+        v.skip = false;
+        v.fp = fp != 0;
+        v.pd = (double)v.p.q;
+        v.pi = 1.0 / v.pd;
+        v.pinvd = (double)v.pinv.x;
+        return v;
+    }
+};
+
 // Rescale INTT of the last limb: src limb (L-1) of poly s -> last[s], canonical.
 struct JobLastInv
 {

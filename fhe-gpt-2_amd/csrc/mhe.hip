@@ -218,6 +218,10 @@ struct Workspace
     // sum of the lifted special limbs T [2][L][n], L = rs_limbs; allocated by the first call
     Scratch rs_base;
     int rs_limbs = 0;
+    // mhe_relin_sum_rescale: per group in flight (MHE_MAXB) A [2][L+1][n], T [2][L][n] and the sum of
+    // the products' first two polys C [2][L][n], L = ps_limbs; allocated by the first call
+    Scratch ps_base;
+    int ps_limbs = 0;
     // kernel timing (mhe_ctx_set_timing): event pairs recorded around the two dominant
     // key-switch kernels on this stream, read back by mhe_kernel_time
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[2];
@@ -229,6 +233,7 @@ struct Workspace
         base.release();
         hoist_base.release();
         rs_base.release();
+        ps_base.release();
         if (flags) (void)hipFree(flags);
         flags = nullptr;
         for (auto &v : ev)
@@ -291,6 +296,7 @@ struct mhe_ctx
     std::atomic<int> fail_switch{ 0 }; // mhe_debug_fail_switch: the n-th next batched key switch fails (0: off)
     std::atomic<unsigned long long> hoist_rot{ 0 }, hoist_mac{ 0 }, hoist_bad{ 0 }; // mhe_hoist_stats
     std::atomic<unsigned long long> rotsum_sums{ 0 }, rotsum_terms{ 0 };             // mhe_rotsum_stats
+    std::atomic<unsigned long long> prodsum_sums{ 0 }, prodsum_terms{ 0 };           // mhe_prodsum_stats
     std::atomic<int> fail_alloc{ 0 }; // mhe_debug_fail_alloc: the n-th next allocation fails (0: off)
     TwF *cmodf = nullptr; // [K][K]: (q_j mod q_i, (q_j mod q_i) / q_i) as doubles, j major (hoist.h)
     std::mutex mask_mu;
@@ -1194,7 +1200,7 @@ MHE_EXPORT int mhe_scratch_bytes(mhe_ctx *c, uint64_t *workspace, uint64_t *hois
         *workspace = *hoisting = 0;
         for (auto &kv : c->ws)
         {
-            *workspace += kv.second.base.bytes + kv.second.rs_base.bytes;
+            *workspace += kv.second.base.bytes + kv.second.rs_base.bytes + kv.second.ps_base.bytes;
             *hoisting += kv.second.hoist_base.bytes;
         }
         *streams = (int)c->ws.size();
@@ -1722,6 +1728,9 @@ MHE_EXPORT int mhe_apply_galois_to(mhe_ctx *c, const uint64_t *in, uint64_t *out
 
 // ------------------------------------------ batched rotations, hoisting and rotate-and-sum
 #include "rotate.h"
+
+// ------------------------------------------------- sums of relinearized products, rescaled
+#include "prodsum.h"
 
 MHE_EXPORT int mhe_rescale_batch(mhe_ctx *c, int count, const uint64_t *const *in, uint64_t *const *out, int size,
                                  int limbs, void *s)

@@ -755,6 +755,14 @@ private:
 void set_batched_launches(bool on);
 bool batched_launches();
 
+// (not SEAL API) Merged product sums, off by default (MHE_PRODSUM=1 in the environment starts it
+// on).  On, the callers that multiply, add and rescale -- the composite polynomials' depth loop
+// (comp.cpp), the Chebyshev bands and combines of the bootstrapping's modular reduction (boot.cpp)
+// and the packed products of the GPT-2 block -- issue Evaluator::multiply_sum_rescale instead of
+// multiply_reduced_error_many, the adds and rescale_to_next_inplace_many: the same words and scales.
+void set_merged_product_sums(bool on);
+bool merged_product_sums();
+
 // (not SEAL API) How many merged Lockstep / FiberBatch calls failed and were re-run member by
 // member (Evaluator::lockstep_execute), process-wide; reset: return the count and start from 0.
 // A healthy run reports 0: the engine's allocation retries and failures are in mhe_alloc_stats.
@@ -915,6 +923,23 @@ public:
     void multiply_reduced_error_many(const std::vector<const Ciphertext *> &encrypted1,
                                      const std::vector<const Ciphertext *> &encrypted2, const RelinKeys &relin_keys,
                                      const std::vector<Ciphertext *> &destinations) const;
+    // (not SEAL API) sums of products, rescaled.  group[i] is the sum that product i belongs to
+    // (non-decreasing from 0, no sum empty; one destination and one entry of twice per sum).  By
+    // definition the sequence: p_i = multiply_reduced_error(*encrypted1[i], *encrypted2[i]); per sum
+    // d = its first p, add_inplace_reduced_error(d, p) for its further terms in order,
+    // add_inplace_reduced_error(d, d) when twice[g]; rescale_to_next_inplace(d); *destinations[g] = d
+    // -- its words, scale, parms_id and exceptions.  Sums whose products end at one level run as one
+    // mhe_relin_sum_rescale per level: every product keeps its own key switch up to the lift of its
+    // special limb, and one forward NTT per limb serves the ModDown and the rescale of the whole sum.
+    // Batched launches off, an enabled trace, a sum whose products end at different levels, an input
+    // that is not size 2 or not in NTT form, or a product level of one limb run the sequence itself
+    // (multiply_reduced_error_many, the adds, rescale_to_next_inplace_many; a traced run records
+    // their records).  Destinations must be distinct objects, none of them an input; when the call
+    // throws they keep their contents.
+    void multiply_sum_rescale(const std::vector<const Ciphertext *> &encrypted1,
+                              const std::vector<const Ciphertext *> &encrypted2, const std::vector<int> &group,
+                              const std::vector<bool> &twice, const RelinKeys &relin_keys,
+                              const std::vector<Ciphertext *> &destinations) const;
     void complex_conjugate_inplace(Ciphertext &encrypted, const GaloisKeys &galois_keys, MemoryPoolHandle = {}) const;
     void complex_conjugate(const Ciphertext &encrypted, const GaloisKeys &galois_keys, Ciphertext &destination,
                            MemoryPoolHandle = {}) const;
@@ -1028,6 +1053,12 @@ private:
     // rotate_sum of every op (one mhe_rotate_sum, one group per op); false, with nothing written,
     // when an op has to take the one-by-one path
     bool rotate_sum_merged(const std::vector<LsOp *> &ops) const;
+    // multiply_sum_rescale through mhe_relin_sum_rescale (one call per level); false, with nothing
+    // written, when the sequence has to run instead.  Every sum goes through a temporary.
+    bool multiply_sum_merged(const std::vector<const Ciphertext *> &encrypted1,
+                             const std::vector<const Ciphertext *> &encrypted2, const std::vector<int> &group,
+                             const std::vector<bool> &twice, const RelinKeys &relin_keys,
+                             const std::vector<Ciphertext *> &destinations) const;
     SEALContext context_;
     CKKSEncoder &encoder_;
     struct VecCache;

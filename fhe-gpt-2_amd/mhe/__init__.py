@@ -91,6 +91,10 @@ SIGNATURES = {
                                       ctypes.c_int, ctypes.c_int, vp]),
     "mhe_rotsum_stats": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
                                         ctypes.c_int]),
+    "mhe_relin_sum_rescale": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
+                                             ctypes.POINTER(ctypes.c_int), vp, ctypes.c_int, vp, ctypes.c_int, vp]),
+    "mhe_prodsum_stats": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                         ctypes.c_int]),
     "mhe_switch_key_batch": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
                                             vp]),
     "mhe_mod_switch_drop": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.c_int, vp]),
@@ -497,6 +501,28 @@ class Engine:
         """mhe_rotsum_stats: (groups summed, entries rotated) by rotate_sum."""
         s, t = ctypes.c_uint64(), ctypes.c_uint64()
         _check(lib().mhe_rotsum_stats(self._h, ctypes.byref(s), ctypes.byref(t), 1 if reset else 0))
+        return s.value, t.value
+
+    def relin_sum_rescale(self, ct3s, key, key_limbs=None, groups=None, twice=None, outs=None):
+        """mhe_relin_sum_rescale: outs[g] = rescale((2 if twice[g] else 1) * the sum of the relinearized
+        products of group g) (groups[i]: the group of product i, non-decreasing from 0; None: one
+        group), one forward NTT per limb per group behind the key switches."""
+        cnt = len(ct3s)
+        groups = [0] * cnt if groups is None else [int(g) for g in groups]
+        ng = (max(groups) + 1) if groups else 0
+        L = ct3s[0].shape[1] if ct3s else (outs[0].shape[1] + 1 if outs else 2)
+        outs = [self.empty(2, L - 1, self.n) for _ in range(ng)] if outs is None else outs
+        gr = (ctypes.c_int * cnt)(*groups)
+        tw = None if twice is None else (ctypes.c_int * len(twice))(*[1 if t else 0 for t in twice])
+        kl = self._key_limbs(key) if key_limbs is None else int(key_limbs)
+        _check(lib().mhe_relin_sum_rescale(self._h, cnt, self._ptrs(ct3s), gr, len(outs), tw, _ptr(key), kl,
+                                           self._ptrs(outs), L, self.stream()))
+        return outs
+
+    def prodsum_stats(self, reset=False):
+        """mhe_prodsum_stats: (groups, terms) that took relin_sum_rescale's merged path."""
+        s, t = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().mhe_prodsum_stats(self._h, ctypes.byref(s), ctypes.byref(t), 1 if reset else 0))
         return s.value, t.value
 
     def rescale_batch(self, cts, outs=None):

@@ -279,6 +279,23 @@ void Polynomial::read_heap_from_file(std::istream &in)
     }
 }
 
+// mo[i] = rescale_to_next(multiply_reduced_error(m1[i], m2[i])) in batched launches; with merged
+// product sums on (seal::set_merged_product_sums) as one call, every product a sum of one term
+static void products_rescaled(Evaluator &evaluator, const std::vector<const Ciphertext *> &m1,
+                              const std::vector<const Ciphertext *> &m2, RelinKeys &relin_keys,
+                              const std::vector<Ciphertext *> &mo)
+{
+    if (merged_product_sums() && !mo.empty())
+    {
+        std::vector<int> group(mo.size());
+        for (std::size_t i = 0; i < mo.size(); i++) group[i] = (int)i;
+        evaluator.multiply_sum_rescale(m1, m2, group, std::vector<bool>(mo.size(), false), relin_keys, mo);
+        return;
+    }
+    evaluator.multiply_reduced_error_many(m1, m2, relin_keys, mo);
+    evaluator.rescale_to_next_inplace_many(mo);
+}
+
 void Polynomial::homomorphic_poly_evaluation(SEALContext &, CKKSEncoder &, Encryptor &, Evaluator &evaluator,
                                              RelinKeys &relin_keys, Ciphertext &rtn, Ciphertext &cipher, Decryptor &)
 {
@@ -370,8 +387,7 @@ void Polynomial::homomorphic_poly_evaluation(SEALContext &, CKKSEncoder &, Encry
             m2.push_back(&baby[i - lpow2]);
             mo.push_back(&baby[i]);
         }
-        evaluator.multiply_reduced_error_many(m1, m2, relin_keys, mo);
-        evaluator.rescale_to_next_inplace_many(mo);
+        products_rescaled(evaluator, m1, m2, relin_keys, mo);
         for (long i : band)
         {
             const long lpow2 = 1L << (int)std::floor(std::log(i) / std::log(2));
@@ -485,8 +501,7 @@ void Polynomial::homomorphic_poly_evaluation(SEALContext &, CKKSEncoder &, Encry
                 mo.push_back(&cipherheap[i]);
             }
         }
-        evaluator.multiply_reduced_error_many(m1, m2, relin_keys, mo);
-        evaluator.rescale_to_next_inplace_many(mo);
+        products_rescaled(evaluator, m1, m2, relin_keys, mo);
         for (long i : prod) evaluator.add_reduced_error(cipherheap[i], cipherheap[2 * (i + 1)], cipherheap[i]);
         gindex++;
     }

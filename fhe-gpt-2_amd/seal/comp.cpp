@@ -344,20 +344,44 @@ void eval_polynomial_integrate(Encryptor &encryptor, Evaluator &evaluator, Decry
             if (i <= tree.m - 1) add_step(pow2(i), pow2(i - 1), pow2(i - 1), 0);
             if (i <= tree.l)
                 for (long j = pow2(i - 1) + 1; j <= pow2(i) - 1; j += 2) add_step(j, pow2(i - 1), j - pow2(i - 1), pow2(i) - j);
-            evaluator.multiply_reduced_error_many(m1, m2, relin_keys, mo);
+            if (merged_product_sums() && !m1.empty())
+            {
+                // the same sequence as one call: a spine is the sum of its products, a step one
+                // product doubled (m1 / m2 hold the spines' terms spine by spine, then the steps)
+                std::vector<int> group;
+                std::vector<bool> twice;
+                std::vector<Ciphertext *> sums;
+                for (Spine &sp : spines)
+                {
+                    group.insert(group.end(), 1 + sp.terms.size(), (int)sums.size());
+                    twice.push_back(false);
+                    sums.push_back(pt[sp.j].get());
+                }
+                for (Step &st : steps)
+                {
+                    group.push_back((int)sums.size());
+                    twice.push_back(true);
+                    sums.push_back(st.prod.get());
+                }
+                evaluator.multiply_sum_rescale(m1, m2, group, twice, relin_keys, sums);
+            }
+            else
+            {
+                evaluator.multiply_reduced_error_many(m1, m2, relin_keys, mo);
 
-            resc.clear();
-            for (Spine &sp : spines)
-            {
-                for (Ciphertext *t : sp.terms) evaluator.add_inplace_reduced_error(*pt[sp.j], *t);
-                resc.push_back(pt[sp.j].get());
+                resc.clear();
+                for (Spine &sp : spines)
+                {
+                    for (Ciphertext *t : sp.terms) evaluator.add_inplace_reduced_error(*pt[sp.j], *t);
+                    resc.push_back(pt[sp.j].get());
+                }
+                for (Step &st : steps)
+                {
+                    evaluator.add_inplace_reduced_error(*st.prod, *st.prod);
+                    resc.push_back(st.prod.get());
+                }
+                evaluator.rescale_to_next_inplace_many(resc);
             }
-            for (Step &st : steps)
-            {
-                evaluator.add_inplace_reduced_error(*st.prod, *st.prod);
-                resc.push_back(st.prod.get());
-            }
-            evaluator.rescale_to_next_inplace_many(resc);
             for (Spine &sp : spines) evaluator.add_inplace_reduced_error(*pt[sp.j], need(pt[sp.kend], "pt[k]"));
             for (Step &st : steps)
             {

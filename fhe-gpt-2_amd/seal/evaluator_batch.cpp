@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cstdlib>
 #include <map>
 
 namespace seal
@@ -14,6 +15,9 @@ namespace
 {
 std::atomic<bool> g_batched{ true };
 std::atomic<std::uint64_t> g_merged_fallbacks{ 0 };
+const char *mulsum_fault(const std::vector<const Ciphertext *> &e1, const std::vector<const Ciphertext *> &e2,
+                         const std::vector<int> &group, const std::vector<bool> &twice,
+                         const std::vector<Ciphertext *> &dst); // (with multiply_sum_rescale below)
 } // namespace
 void set_batched_launches(bool on)
 {
@@ -57,6 +61,7 @@ void Evaluator::lockstep_execute(std::vector<LsOp *> &ops) const
                     multiply_reduced_error(*o.in[0], *o.in2[0], *o.rk, *o.out[0]);
                 break;
             case LsOp::ROTSUM: rotate_sum(o.in, o.steps, *o.gk, *o.out[0]); break;
+            case LsOp::MULSUM: multiply_sum_rescale(o.in, o.in2, o.steps, o.twice, *o.rk, o.out); break;
             }
         }
         catch (...)
@@ -72,6 +77,22 @@ void Evaluator::lockstep_execute(std::vector<LsOp *> &ops) const
         std::vector<const Ciphertext *> in, in2;
         std::vector<int> steps;
         std::vector<Ciphertext *> dst;
+        if (kind == LsOp::MULSUM)
+        {
+            // the members' sums concatenated; a member whose own call would throw for its arguments
+            // makes all run alone
+            std::vector<bool> twice;
+            for (LsOp *o : ops)
+            {
+                if (mulsum_fault(o->in, o->in2, o->steps, o->twice, o->out)) return false;
+                for (int g : o->steps) steps.push_back(g + (int)dst.size());
+                in.insert(in.end(), o->in.begin(), o->in.end());
+                in2.insert(in2.end(), o->in2.begin(), o->in2.end());
+                twice.insert(twice.end(), o->twice.begin(), o->twice.end());
+                dst.insert(dst.end(), o->out.begin(), o->out.end());
+            }
+            return multiply_sum_merged(in, in2, steps, twice, *ops[0]->rk, dst);
+        }
         for (LsOp *o : ops)
         {
             in.insert(in.end(), o->in.begin(), o->in.end());
@@ -419,6 +440,162 @@ void Evaluator::multiply_reduced_error_many(const std::vector<const Ciphertext *
     }
     relinearize_inplace_many(destinations, relin_keys);
     tr.record("mul_re", destinations);
+}
+
+// ------------------------------------------------------------------------------ product sums
+namespace
+{
+std::atomic<bool> g_prodsum{ [] {
+    const char *e = std::getenv("MHE_PRODSUM");
+    return e && e[0] == '1';
+}() };
+
+// the first fault in the arguments of a multiply_sum_rescale call (all std::invalid_argument), or
+// nullptr: group[] non-decreasing from 0 without a gap, one entry of twice and one destination per
+// sum, no null entry, destinations distinct and none of them an input
+const char *mulsum_fault(const std::vector<const Ciphertext *> &e1, const std::vector<const Ciphertext *> &e2,
+                         const std::vector<int> &group, const std::vector<bool> &twice,
+                         const std::vector<Ciphertext *> &dst)
+{
+    const char *shape = "encrypted1, encrypted2 and group must have the same, nonzero size, and group must number "
+                        "the sums of twice and destinations in order";
+    const std::size_t terms = e1.size();
+    if (terms != e2.size() || terms != group.size() || twice.size() != dst.size() || terms == 0) return shape;
+    for (std::size_t i = 0; i < terms; i++)
+        if (group[i] != (i ? group[i - 1] : 0) && !(i && group[i] == group[i - 1] + 1)) return shape;
+    if ((std::size_t)group.back() + 1 != dst.size()) return shape;
+    for (std::size_t i = 0; i < terms; i++)
+        if (!e1[i] || !e2[i]) return "null ciphertext";
+    for (std::size_t g = 0; g < dst.size(); g++)
+    {
+        if (!dst[g]) return "null ciphertext";
+        for (std::size_t j = 0; j < terms; j++)
+            if (dst[g] == e1[j] || dst[g] == e2[j] || (j < dst.size() && j != g && dst[g] == dst[j]))
+                return "destinations must be distinct and must not be inputs";
+    }
+    return nullptr;
+}
+} // namespace
+void set_merged_product_sums(bool on)
+{
+    g_prodsum.store(on);
+}
+bool merged_product_sums()
+{
+    return g_prodsum.load();
+}
+
+bool Evaluator::multiply_sum_merged(const std::vector<const Ciphertext *> &encrypted1,
+                                    const std::vector<const Ciphertext *> &encrypted2, const std::vector<int> &group,
+                                    const std::vector<bool> &twice, const RelinKeys &relin_keys,
+                                    const std::vector<Ciphertext *> &destinations) const
+{
+    if (!batched_launches() || trace::enabled()) return false;
+    if (relin_keys.parms_id() != context_.key_parms_id()) return false;
+    const std::size_t count = encrypted1.size(), G = destinations.size();
+    // the level every product ends at (the lower operand's), one level per sum
+    std::vector<std::size_t> level(G, 0), last(G, 0);
+    for (std::size_t i = 0; i < count; i++)
+    {
+        const Ciphertext *a = encrypted1[i], *b = encrypted2[i];
+        if (!a || !b || a->size() != 2 || b->size() != 2 || !a->is_ntt_form() || !b->is_ntt_form()) return false;
+        const std::size_t L = std::min(a->coeff_modulus_size(), b->coeff_modulus_size()), g = (std::size_t)group[i];
+        if (L < 2 || (level[g] && level[g] != L)) return false;
+        level[g] = L;
+        last[g] = i;
+    }
+    // the products as multiply_reduced_error_many makes them (size 3)
+    std::vector<Ciphertext> prod(count);
+    for (std::size_t i = 0; i < count; i++)
+    {
+        const Ciphertext &a = *encrypted1[i], &b = *encrypted2[i];
+        if (a.coeff_modulus_size() == b.coeff_modulus_size() && a.parms_id() == b.parms_id())
+            mulre_product(context_, a, b, prod[i]);
+        else
+        {
+            prod[i] = a;
+            reduced_error_op(prod[i], b, Rmode::mul);
+        }
+        if (prod[i].size() != 3 || prod[i].coeff_modulus_size() != level[(std::size_t)group[i]]) return false;
+    }
+    // a sum carries its last term's scale (add_inplace_reduced_error at equal levels) into the rescale
+    std::vector<Rescale> resc;
+    resc.reserve(G);
+    for (std::size_t g = 0; g < G; g++) resc.push_back(check_rescale(context_, prod[last[g]]));
+    void *s = context_.stream();
+    std::map<std::size_t, std::vector<std::size_t>> by_level;
+    for (std::size_t g = 0; g < G; g++) by_level[level[g]].push_back(g);
+    // every level's key before the first launch
+    std::map<std::size_t, std::pair<const std::uint64_t *, int>> key;
+    for (auto &lv : by_level)
+    {
+        std::size_t kl = 0;
+        const std::uint64_t *k = relin_keys.key_for(RelinKeys::get_index(2), lv.first, s, kl);
+        key[lv.first] = { k, (int)kl };
+    }
+    // every sum into a fresh store, committed to a temporary after its launch and moved to its
+    // destination after the last: a call that throws leaves every destination as it was
+    std::vector<Ciphertext> res(G);
+    std::vector<std::size_t> first(G, count);
+    for (std::size_t i = count; i-- > 0;) first[(std::size_t)group[i]] = i;
+    for (auto &lv : by_level)
+    {
+        const std::size_t L = lv.first;
+        std::vector<const std::uint64_t *> ct3;
+        std::vector<int> grp, tw;
+        std::vector<std::uint64_t *> out;
+        std::vector<Placed> staged;
+        staged.reserve(lv.second.size());
+        for (std::size_t g : lv.second)
+        {
+            for (std::size_t i = first[g]; i <= last[g]; i++)
+            {
+                ct3.push_back(prod[i].store().dev_read(s));
+                grp.push_back((int)tw.size());
+            }
+            tw.push_back(twice[g] ? 1 : 0);
+            staged.emplace_back(context_, Placed::fresh, prod[last[g]], res[g], 2, L - 1);
+            out.push_back(staged.back().out(s));
+        }
+        chk(mhe_relin_sum_rescale(context_.engine(), (int)ct3.size(), ct3.data(), grp.data(), (int)out.size(), tw.data(),
+                                  key[L].first, key[L].second, out.data(), (int)L, s));
+        for (std::size_t k = 0; k < lv.second.size(); k++)
+            staged[k].commit(resc[lv.second[k]].next, resc[lv.second[k]].scale);
+    }
+    for (std::size_t g = 0; g < G; g++) *destinations[g] = std::move(res[g]);
+    return true;
+}
+
+void Evaluator::multiply_sum_rescale(const std::vector<const Ciphertext *> &encrypted1,
+                                     const std::vector<const Ciphertext *> &encrypted2, const std::vector<int> &group,
+                                     const std::vector<bool> &twice, const RelinKeys &relin_keys,
+                                     const std::vector<Ciphertext *> &destinations) const
+{
+    const auto make = [&] {
+        LsOp op{ LsOp::MULSUM, encrypted1, encrypted2, group, destinations, nullptr, &relin_keys };
+        op.twice = twice;
+        return op;
+    };
+    if (merge_point(make)) return;
+    if (const char *f = mulsum_fault(encrypted1, encrypted2, group, twice, destinations)) throw std::invalid_argument(f);
+    if (multiply_sum_merged(encrypted1, encrypted2, group, twice, relin_keys, destinations)) return;
+    // the sequence itself: the products (relinearizations batched), each sum folded in order and
+    // doubled, the rescales batched
+    std::vector<Ciphertext> p(encrypted1.size());
+    std::vector<Ciphertext *> pp, sums;
+    for (Ciphertext &c : p) pp.push_back(&c);
+    multiply_reduced_error_many(encrypted1, encrypted2, relin_keys, pp);
+    for (std::size_t i = 0; i < p.size(); i++)
+    {
+        if (i == 0 || group[i] != group[i - 1])
+            sums.push_back(&p[i]);
+        else
+            add_inplace_reduced_error(*sums.back(), p[i]);
+        if ((i + 1 == p.size() || group[i + 1] != group[i]) && twice[(std::size_t)group[i]])
+            add_inplace_reduced_error(*sums.back(), *sums.back());
+    }
+    rescale_to_next_inplace_many(sums);
+    for (std::size_t g = 0; g < sums.size(); g++) *destinations[g] = std::move(*sums[g]);
 }
 
 void Evaluator::rescale_to_next_inplace_many(const std::vector<Ciphertext *> &encrypted) const

@@ -224,6 +224,14 @@ void products(const std::vector<const Ciphertext *> &a, const std::vector<const 
     prods.assign(a.size(), Ciphertext());
     std::vector<Ciphertext *> p;
     for (auto &c : prods) p.push_back(&c);
+    if (seal::merged_product_sums() && !a.empty())
+    {
+        // the same two calls as one: every product a sum of one term
+        std::vector<int> group(a.size());
+        for (std::size_t b = 0; b < a.size(); b++) group[b] = (int)b;
+        o.evaluator.multiply_sum_rescale(a, w, group, std::vector<bool>(a.size(), false), o.relin_keys, p);
+        return;
+    }
     o.evaluator.multiply_reduced_error_many(a, w, o.relin_keys, p);
     o.evaluator.rescale_to_next_inplace_many(p);
 }

@@ -195,7 +195,15 @@ void mulre_product(const SEALContext &ctx, const Ciphertext &a, const Ciphertext
 // lockstep_execute and a merge_point() line in its entry point.
 struct LsOp
 {
-    enum Kind { ROT, RESC, RELIN, MULRE, ROTSUM /* in / steps: the terms, out[0]: the sum */ } kind = ROT;
+    enum Kind
+    {
+        ROT,
+        RESC,
+        RELIN,
+        MULRE,
+        ROTSUM, // in / steps: the terms, out[0]: the sum
+        MULSUM  // in / in2: the factors, steps: each product's sum, twice / out: per sum
+    } kind = ROT;
     std::vector<const Ciphertext *> in, in2;
     std::vector<int> steps;
     std::vector<Ciphertext *> out;
@@ -203,6 +211,7 @@ struct LsOp
     const RelinKeys *rk = nullptr;
     const Evaluator *ev = nullptr;
     std::exception_ptr err{};
+    std::vector<bool> twice{};
 };
 
 // The merging state is thread-local and private to lockstep.cpp; the other units read it through

@@ -301,6 +301,35 @@ int mhe_rotate_sum(mhe_ctx *ctx, int count, const uint64_t *const *in, const uin
                    const uint64_t *const *keys, const int *key_limbs, const int *group, int groups,
                    uint64_t *const *out, int accumulate, int limbs, void *stream);
 int mhe_rotsum_stats(mhe_ctx *ctx, uint64_t *sums, uint64_t *terms, int reset);
+/* Relinearize, sum and rescale (no SEAL counterpart; the spines and doubled steps of the composite
+ * polynomials and every product that is rescaled at once): ct3[i] is [3][L][n] in NTT form, as
+ * mhe_ct_multiply / mhe_ct_square write it, and is left unchanged;
+ * out[g][2][L-1][n] = rescale_to_next((twice[g] ? 2 : 1) * sum over the entries i of group g of
+ * relinearize(ct3[i])) -- the words of mhe_relinearize on each product, mhe_add over the group
+ * (add_inplace_reduced_error at equal levels), the sum added to itself when twice[g], and
+ * mhe_rescale_to_next, with one forward NTT per limb per group behind the key switches instead of
+ * one ModDown per product and one rescale.  twice may be NULL (no group doubled).  group[] follows
+ * mhe_rotate_sum's rule; limbs >= 2; outputs disjoint from every input and from each other.
+ * The identity: with (d0, d1, d2)^k the product of term k, acc^k[j][0..L] the key products of d2^k,
+ * t^k_{j,i} SEAL's ModDown lift of INTT_P(acc^k[j][L]) to q_i (evaluator.cpp:2466-2524) and
+ * m = twice ? 2 : 1, let C = m sum_k d^k, A = m sum_k acc^k and T = m sum_k t^k, all mod q_i.  The sum
+ * of the sequence is S_{j,i} = C_{j,i} + (A_{j,i} - NTT_i(T_{j,i})) P^-1, and with r_{j,i} the rescale's
+ * lift of INTT(S_{j,L-1}) (util/rns.cpp:737-808)
+ *     out_{j,i} = (C_{j,i} + A_{j,i} P^-1 - NTT_i(T_{j,i} P^-1 + r_{j,i})) q_{L-1}^-1  (mod q_i), i < L-1.
+ * Every relinearization keeps its own key switch, its own inverse NTT of the special limb and its own
+ * lift; T is summed after the lift, per data prime.  (Special limbs are never added mod P: that would
+ * lose the carry.)
+ * All arguments are checked and all scratch is grown before the first launch: a failed call leaves
+ * every out[g] as it was.  A, T and C ((6L + 2) n words per group slot, 8 slots) are allocated by the
+ * first call on a stream and grown by the first call at a higher level, so capturing a call into a
+ * graph needs one warm call of that level on the stream first.  mhe_op_counts sees the sequence's op
+ * mix: count key switches, 2 (terms - 1 + twice) additions and 2 rescales per group, at L.
+ * mhe_prodsum_stats: groups and terms that went through the merged path since the last reset (the
+ * separate-MAC debugging path, MHE_KS_FUSED=0, runs the sequence entry by entry and counts nothing). */
+int mhe_relin_sum_rescale(mhe_ctx *ctx, int count, const uint64_t *const *ct3, const int *group, int groups,
+                          const int *twice, const uint64_t *relin_key, int key_limbs, uint64_t *const *out, int limbs,
+                          void *stream);
+int mhe_prodsum_stats(mhe_ctx *ctx, uint64_t *sums, uint64_t *terms, int reset);
 /* mhe_rescale_to_next for each i: in[i][size][L][n] -> out[i][size][L-1][n]. */
 int mhe_rescale_batch(mhe_ctx *ctx, int count, const uint64_t *const *in, uint64_t *const *out, int size, int limbs,
                       void *stream);

@@ -6,6 +6,9 @@ stream: rescale (1 and 4 ciphertexts per launch), key switch / relinearize (1 an
 rotaddGxT / rotsumGxT (--rotsum GxT): the giant-step sums of G images, T rotations of distinct inputs
 each with T keys shared over the images -- mhe_apply_galois_batch + T - 1 mhe_add per sum against one
 mhe_rotate_sum.
+prodseqGxT / prodsumGxT (--ops prodseq,prodsum --prodsum GxT[d],...): G sums of T products, doubled with
+a trailing d -- mhe_ct_multiply, mhe_switch_key_batch, the mhe_adds and mhe_rescale_batch against
+mhe_ct_multiply and one mhe_relin_sum_rescale; words compared first, interleaved rounds (prod_bench).
 Used for A/B runs of library variants (MHE_LIB_PATH=build/var/NAME/libmhe.so).
 
     python scripts/ubench_ops.py [--limbs 31] [--reps 50]
@@ -25,6 +28,71 @@ import torch  # noqa: E402
 import mhe  # noqa: E402
 
 
+def prod_bench(eng, rnd, key, L, n, shape, reps, rounds, st):
+    """prodseq against prodsum for G sums of T products (shape "GxT", a trailing d: every sum doubled).
+    prodseq is the sequence the merged call replaces: mhe_ct_multiply per product, one
+    mhe_switch_key_batch, the mhe_adds of every sum, one mhe_rescale_batch.  prodsum: the same
+    products, then one mhe_relin_sum_rescale.  The legs' words are compared first; then `rounds`
+    interleaved rounds of HIP events around `reps` calls after 3 warm-ups.  One JSON line per leg and
+    round, then one with the medians and each leg's spread (max - min over its rounds)."""
+    dbl = shape.endswith("d")
+    G, T = (int(x) for x in shape.rstrip("d").split("x"))
+    a = [rnd(2, L, n, limbs=L) for _ in range(G * T)]
+    b = [rnd(2, L, n, limbs=L) for _ in range(G * T)]
+    ct3 = [eng.empty(3, L, n) for _ in range(G * T)]
+    groups = [g for g in range(G) for _ in range(T)]
+    out_seq = [eng.empty(2, L - 1, n) for _ in range(G)]
+    out_sum = [eng.empty(2, L - 1, n) for _ in range(G)]
+
+    def products():
+        for x, y, c in zip(a, b, ct3):
+            eng.multiply(x, y, c)
+
+    def prodseq():
+        products()
+        eng.switch_key_batch([c[:2] for c in ct3], [c[2] for c in ct3], [key] * len(ct3))
+        sums = []
+        for g in range(G):
+            s = ct3[g * T][:2]
+            for t in range(1, T):
+                eng.add(s, ct3[g * T + t][:2], s)
+            if dbl:
+                eng.add(s, s, s)
+            sums.append(s)
+        eng.rescale_batch(sums, out_seq)
+
+    def prodsum():
+        products()
+        eng.relin_sum_rescale(ct3, key, groups=groups, twice=[dbl] * G, outs=out_sum)
+
+    legs = {"prodseq": prodseq, "prodsum": prodsum}
+    prodseq()
+    prodsum()
+    torch.cuda.synchronize()
+    if not all(torch.equal(x, y) for x, y in zip(out_seq, out_sum)):
+        raise SystemExit(f"prodseq and prodsum differ at {shape}, {L} limbs")
+    us = {k: [] for k in legs}
+    for r in range(rounds):
+        for name, f in legs.items():
+            for _ in range(3):
+                f()
+            torch.cuda.synchronize()
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record(st)
+            for _ in range(reps):
+                f()
+            t1.record(st)
+            torch.cuda.synchronize()
+            us[name].append(t0.elapsed_time(t1) * 1000 / reps)
+            print(json.dumps({"op": name + shape, "limbs": L, "round": r, "us": round(us[name][-1], 2)}), flush=True)
+    med = {k: float(np.median(v)) for k, v in us.items()}
+    print(json.dumps({"op": "prod" + shape, "limbs": L, "words_equal": True,
+                      "prodseq_us": round(med["prodseq"], 2), "prodsum_us": round(med["prodsum"], 2),
+                      "prodseq_spread_us": round(max(us["prodseq"]) - min(us["prodseq"]), 2),
+                      "prodsum_spread_us": round(max(us["prodsum"]) - min(us["prodsum"]), 2),
+                      "ratio": round(med["prodsum"] / med["prodseq"], 4)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--limbs", type=int, default=31)
@@ -33,6 +101,10 @@ def main():
     ap.add_argument("--bsgs", default="8x7", help="inputs x rotations of the bsgs op (keys shared over inputs)")
     ap.add_argument("--rotsum", default="1x8", help="sums x rotations per sum of the rotadd / rotsum ops")
     ap.add_argument("--hoist", type=int, default=None, help="hoisted rotations on (1) / off (0); default: the context's")
+    ap.add_argument("--prodsum", default="8x1,8x1d,1x8,4x2",
+                    help="sums x products per sum of the prodseq / prodsum ops, comma-separated; a trailing d: doubled")
+    ap.add_argument("--prod-reps", type=int, default=20, help="calls per timed round of prodseq / prodsum")
+    ap.add_argument("--rounds", type=int, default=3, help="interleaved rounds of prodseq / prodsum")
     a = ap.parse_args()
     log_n, n = 16, 1 << 16
     bits = [51] + [46] * 16 + [51] * 14 + [51]
@@ -107,7 +179,13 @@ def main():
         "mulplain": lambda: eng.multiply_plain(cts[0], cts[2][0], rot_out[0]),
     }
     st = torch.cuda.current_stream(eng.torch_device)
-    for name in a.ops.split(","):
+    names = a.ops.split(",")
+    if "prodseq" in names or "prodsum" in names:
+        # both legs always run: their words are compared first, and the rounds interleave them
+        for shape in a.prodsum.split(","):
+            prod_bench(eng, rnd, keys[0], L, n, shape, a.prod_reps, a.rounds, st)
+        names = [x for x in names if x not in ("prodseq", "prodsum")]
+    for name in names:
         f = ops[name]
         for _ in range(3):
             f()
