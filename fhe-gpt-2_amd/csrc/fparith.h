@@ -18,9 +18,50 @@
 //   |x| <= 2^53 is within [-q/2 - 1, q/2 + 1].  Forward: x' = red(x) + r, y' = red(x) - r, so
 //   |.| <= 2q + 1 is preserved.  Inverse: x' = red(x + y), y' = mulmod(red(x - y), w), |.| <= q.
 //   (scripts/ubench_bfly.hip checks 1536 random stages at q ~ 2^51 against the integer path.)
+//
+// Unreduced lifts (ntt.h k_modup_col; tests/fp_bounds.cpp checks each figure on the host).  The
+// ModUp lifts a canonical residue x of the digit's prime, 0 <= x < q_J, to the output prime q
+// and runs the 8 stages of the column pass on it:
+//   lazy (q < 2^47): x enters as it stands when q_J <= 4q, so |x| < 4q, and reduced (|x| <=
+//     q/2 + 1) otherwise.  No stage reduces x, every product is within 1.5q, so after stage s
+//     (1..8) |.| <= 4q + 1.5q s, at most 16q <= 2^51 after the 8th: every y that enters
+//     fp_mulmod stays within 2^51 (its limit, below), and every sum is an exact integer below
+//     2^53.  The exit reduces (fp_to_s48, fp_canon: |x| <= 2^52).
+//   lazy, q < 2^46, packed exit: the 8th stage reduces x as fwd_bfly_f does (its x and y are
+//     within 4q + 10.5q = 14.5q), so |x'|, |y'| <= q/2 + 1 + 1.5q = 2q + 1 <= 2^47 - 1: a
+//     signed 48-bit value with no further reduction (fp_s48_of).  The fused MAC's lazy row pass
+//     then starts from |x| <= 2q + 1 <= 4q, ends within 14q + 1 < 16q, and its lazy products
+//     take |a| <= 2^51 as before.
+//   non-lazy (q < 2^51): x enters as it stands when q_J <= 2q, so |x|, |y| < 2q.  The first
+//     stage reduces x itself (|x| <= 2^53) and takes |y| <= 2q into fp_mulmod, the bound B of
+//     the paragraph above; from there on |.| <= 2q + 1 as for reduced input.
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stdint.h>
+#ifdef MHE_FPARITH_HOST
+// Host build of the same functions (the bound check's stand-alone program): no HIP headers, the
+// bit casts through memcpy.
+#include <string.h>
+#define __device__
+#define __forceinline__ inline
+struct double2
+{
+    double x, y;
+};
+static inline double __longlong_as_double(long long v)
+{
+    double d;
+    memcpy(&d, &v, 8);
+    return d;
+}
+static inline long long __double_as_longlong(double d)
+{
+    long long v;
+    memcpy(&v, &d, 8);
+    return v;
+}
+#else
+#include <hip/hip_runtime.h>
+#endif
 
 // Twiddle as (w, w/q).
 typedef double2 TwF;
@@ -30,7 +71,13 @@ __device__ __forceinline__ double fp_rint(double x)
     return __builtin_rint(x);
 }
 
-// y*w mod q in (-1.5q, 1.5q) for |y| <= 4q, w in [0, q), ws = w/q.
+// y*w mod q for w in [0, q), ws = fl(w/q); |result| <= 1.5q in both regimes of |y| below.  The
+// quotient k = rint(fl(y*ws)) differs from y*w/q by at most |y| 2^-54 (ws < 1 against w/q) +
+// |y| 2^-53 (the product's rounding) + 1/2 (rint), and r = y*w - k*q is that many q:
+//   non-lazy butterflies, q < 2^51: |y| <= 2q + 1 < 2^52 (the header's B; an unreduced lift is
+//     below 2q): at most 0.75 + 0.5 = 1.25;
+//   lazy butterflies, q < 2^47: |y| <= 16q <= 2^51: at most 0.375 + 0.5 = 0.875.
+// ("Unreduced lifts" in the header says who enters with what.)
 __device__ __forceinline__ double fp_mulmod(double y, double w, double ws, double q)
 {
     const double h = y * w;
@@ -93,6 +140,13 @@ __device__ __forceinline__ uint64_t fp_to_s48(double x, double q, double qinv)
     return (uint64_t)__double_as_longlong(r + 6755399441055744.0); // 1.5 * 2^52
 }
 
+// The same packing of a value already within the slot: |x| < 2^47, an integer (k_modup_col's folded
+// exit, "Unreduced lifts" above).
+__device__ __forceinline__ uint64_t fp_s48_of(double x)
+{
+    return (uint64_t)__double_as_longlong(x + 6755399441055744.0); // 1.5 * 2^52
+}
+
 // ... and back: flipping bit 47 of r mod 2^48 gives r + 2^47 in [0, 2^48); OR-ed under the exponent
 // of 2^52 (one XOR with both) and less 2^52 + 2^47, that is r exactly.
 __device__ __forceinline__ double fp_from_s48(uint64_t v48)
@@ -111,7 +165,9 @@ __device__ __forceinline__ void fwd_bfly_f(double &x, double &y, const TwF w, do
 
 // Forward butterfly without reducing x, for q < 2^47: within one pass (<= 8 stages) |x| grows
 // from <= 4q by <= 1.5q per stage to <= 16q <= 2^51, which keeps every product's quotient
-// estimate within 1 (|y| <= 2^51) -- so the centered reduction of x can be skipped.
+// estimate within 1 (|y| <= 2^51) -- so the centered reduction of x can be skipped.  What enters
+// at up to 4q: an unreduced lift of a digit prime q_J <= 4q (k_modup_col), and that kernel's
+// folded exit (<= 2q + 1) read back by the fused MAC ("Unreduced lifts" in the header).
 __device__ __forceinline__ void fwd_bfly_f_lazy(double &x, double &y, const TwF w, double q)
 {
     const double r = fp_mulmod(y, w.x, w.y, q);

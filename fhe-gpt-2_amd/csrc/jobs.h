@@ -96,6 +96,7 @@ struct JobModUpCol
     const PrimeDev *primes;
     const Tw *tw;
     int L, K, log_n, I0;
+    int f64 = 0; // limbs of primes below 2^51 leave as doubles (ntt.h MHE_INTER_F64: the fused FP64 MAC reads them)
     struct View
     {
         const u64 *src;
@@ -104,12 +105,13 @@ struct JobModUpCol
         const Tw *tw;
         bool reduce;
         bool skip;
+        bool f64;
         __device__ u64 load(u32 x) const
         {
             u64 v = src[x];
             return reduce ? barrett64(v, p) : v;
         }
-        __device__ void store(u32 x, u64 v) const { dst[x] = v; }
+        __device__ void store(u32 x, u64 v) const { dst[x] = f64 ? (u64)__double_as_longlong(fp_from_u52(v)) : v; }
     };
     __device__ View view(int y) const
     {
@@ -122,6 +124,7 @@ struct JobModUpCol
         v.tw = tw + ((size_t)pi << log_n);
         v.reduce = prime_at(primes, J).q > v.p.q; // key_modulus[J] <= key_modulus[key_index] -> copy
         v.skip = (I == J);
+        v.f64 = f64 && v.p.q < (1ull << 51);
         return v;
     }
 };

@@ -274,7 +274,8 @@ static int run_switch_key_batch(mhe_ctx *c, const KsJob *jobs, int B, int L, hip
         //      never leave registers; every output prime in one launch (chunks of output primes
         //      sized for the Infinity Cache measured slower at every size).
         // 48-bit intermediate (ntt.h tile16): only k_modup_col writes it, so only with column groups
-        const int pack = (c->ks_pack && c->ks_colgroups > 0) ? 1 : 0;
+        // and it leaves the FP sweeps' other limbs as doubles (MHE_INTER_F64), as the fused MAC reads them
+        const int pack = c->ks_colgroups > 0 ? ((c->ks_pack ? 1 : 0) | MHE_INTER_F64) : 0;
         const KsPtrs kp = ks_ptrs(w, jobs, B, nullptr, nullptr);
         hipEvent_t *tc = timing_slot(c, w, TK_MODUP_COL, st);
         if (c->ks_colgroups > 0)
@@ -283,7 +284,9 @@ static int run_switch_key_batch(mhe_ctx *c, const KsJob *jobs, int B, int L, hip
         {
             JobB<JobModUpCol> j;
             j.per = (L + 1) * L;
-            for (int e = 0; e < B; e++) j.j[e] = JobModUpCol{ w->e[e].coeff, w->e[e].modup, c->primes, c->tw, L, c->K, log_n, 0 };
+            // f64 follows nm_ks, the MAC's arithmetic (its reader), not nm, this pass's own: the store
+            // converts a word below 2^52 whichever butterflies made it
+            for (int e = 0; e < B; e++) j.j[e] = JobModUpCol{ w->e[e].coeff, w->e[e].modup, c->primes, c->tw, L, c->K, log_n, 0, c->nm_ks.fp ? 1 : 0 };
             fwd_col(j, log_n, B * (L + 1) * L, c->nm, st);
         }
         timing_end(tc, st);

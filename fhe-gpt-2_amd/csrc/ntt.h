@@ -104,9 +104,16 @@ __device__ __forceinline__ u32 tile16h(u32 idx)
     const u32 r = idx >> 8, c = idx & 255;
     return ((((r >> 4) << 4) | (c >> 4)) << 8) | (((r & 15) >> 1) << 5) | ((c & 15) << 1) | (r & 1);
 }
+// `pack` of the ModUp column pass: bit 0 = limbs of primes below 2^48 in the 48-bit form above
+// (n = 2^16; the fused MAC must be told the same); bit 1 (MHE_INTER_F64) = the FP sweeps leave every
+// other limb as a double congruent to the residue, |v| <= 2q + 1, instead of the canonical u64.  The
+// fused MAC's FP path (k_ks_row_mac) takes exactly that from a non-packed slot, so every column pass in
+// front of it sets the bit (or, the generic one, JobModUpCol::f64); the hoisted rotations' row pass
+// (JobModUpRowH) reads canonical words and leaves it clear.
+constexpr int MHE_INTER_F64 = 2;
 __device__ __forceinline__ bool inter_packed(int pack, u64 q)
 {
-    return pack && q < (1ull << 48);
+    return (pack & 1) && q < (1ull << 48);
 }
 
 // Forward Harvey butterfly (dwthandler.h:122-125 with ntt.h:34-65 arithmetic).
@@ -257,6 +264,18 @@ struct NttArithF
     __device__ void fwd_tab(T (&v)[E], int gap, const TW *tab, Ix ix) const
     {
         fwd_stage_f<E, LAZY>(v, gap, [&](int e) { return &tab[ix(e)]; }, q, qinv);
+    }
+    // fwd / fwd_tab with the reduction of x whatever LAZY says (k_modup_col: the last stage of a lazy
+    // prime whose exit reduction it replaces)
+    template <int E, class Ix>
+    __device__ void fwd_full(T (&v)[E], int gap, Ix ix) const
+    {
+        fwd_stage_f<E, false>(v, gap, [&](int e) { return &tw[ix(e)]; }, q, qinv);
+    }
+    template <int E, class Ix>
+    __device__ void fwd_tab_full(T (&v)[E], int gap, const TW *tab, Ix ix) const
+    {
+        fwd_stage_f<E, false>(v, gap, [&](int e) { return &tab[ix(e)]; }, q, qinv);
     }
     // fwd_tab on two vectors with one read of each twiddle (fwd_stage_f2)
     template <int E, class Ix>
@@ -799,8 +818,13 @@ __global__ __launch_bounds__(256) void k_inv_col(Job job, int log_n, long long t
 // 1 .. E-1, the same for every lane: read them as scalar loads of the prime's FP table (ftab), issued
 // together, instead of per-stage LDS reads each waited for a few instructions later.  k_modup_col's FP
 // sweeps only: in k_icol_lift / k_col_lift2 it measured equal (profiles/r06s).
+// The phase takes the lifted digit xd (exact doubles of canonical residues of the digit's prime) and
+// leaves the values in v.  red (uniform): xd is first reduced modulo the output prime; without it
+// the first stage reads xd as it stands (the caller's rule: fparith.h, "Unreduced lifts").  The
+// first stage is written in both arms so that neither needs a copy of xd.
 template <int E, int LOGE, class AR>
-__device__ __forceinline__ void fwd_first_phase_s(const AR &ar, typename AR::T (&v)[E], const void *ftab)
+__device__ __forceinline__ void fwd_first_phase_s(const AR &ar, typename AR::T (&v)[E], const double (&xd)[E], bool red,
+                                                  const void *ftab)
 {
     const const_u64_p g = (const_u64_p)ftab;
     typename AR::TW w1[E];
@@ -810,9 +834,28 @@ __device__ __forceinline__ void fwd_first_phase_s(const AR &ar, typename AR::T (
         w1[k].x = __longlong_as_double((long long)g[2 * k]);
         w1[k].y = __longlong_as_double((long long)g[2 * k + 1]);
     }
-#pragma unroll
-    for (int s = 0; s < LOGE; s++)
+    auto stage = [&](int s) {
         ar.template fwd_tab<E>(v, 1 << (LOGE - 1 - s), w1, [&](int e) { return (1 << s) + (e >> (LOGE - s)); });
+    };
+    if (red)
+    {
+#pragma unroll
+        for (int e = 0; e < E; e++) v[e] = fp_reduce(xd[e], ar.q, ar.qinv);
+        stage(0);
+        asm volatile("; lift reduced");
+    }
+    else
+    {
+#pragma unroll
+        for (int e = 0; e < E; e++) v[e] = xd[e];
+        stage(0);
+        // (the markers keep the two arms apart: with their common stage sunk below them, the values
+        // joined through 16 register copies, made in both arms; the copies would show as v_mov_b64 in
+        // front of the branch and in DESIGN.md §18's per-prime instruction counts)
+        asm volatile("; lift as it stands");
+    }
+#pragma unroll
+    for (int s = 1; s < LOGE; s++) stage(s);
 }
 
 // q < 2^47 (the lazy forward butterflies) as a scalar compare of the high word: the compiler folds any
@@ -1172,12 +1215,12 @@ __global__ __launch_bounds__(256, (FP && !MIX) ? MHE_MODUP_OCC : MHE_MODUP_OCC_I
             using TWA = typename AA::TW;
             const TWA *tl = reinterpret_cast<const TWA *>(&twc[(I - i_lo) * R]);
             VT v[E];
-            if constexpr (M != 0)
-            {
-#pragma unroll
-                for (int e = 0; e < E; e++) v[e] = fp_reduce(xd[e], ar.q, ar.qinv);
-            }
-            else
+            // FP, uniform per workgroup: a lazy prime whose packed exit is folded into the last stage
+            // (below), and a non-packed limb left as doubles for the fused MAC
+            const bool packed = inter_packed(pack, p.q);
+            const bool fold = M == 1 && packed && (u32)(p.q >> 32) < (1u << 14); // q < 2^46
+            const bool f64 = M != 0 && (pack & MHE_INTER_F64) != 0;
+            if constexpr (M == 0)
             {
                 const bool red = qJ > p.q; // key_modulus[J] <= key_modulus[I] -> plain copy
 #pragma unroll
@@ -1189,9 +1232,13 @@ __global__ __launch_bounds__(256, (FP && !MIX) ? MHE_MODUP_OCC : MHE_MODUP_OCC_I
             }
             if constexpr (M != 0)
             {
+                // The lift: the digit's canonical residues (< q_J) are reduced modulo q_I only where the
+                // first stage needs it (fparith.h, "Unreduced lifts"): a lazy prime takes |x| <= 4 q_I,
+                // a non-lazy one |y| <= 2 q_I.  (Taken as the difference's sign: every prime is below 2^61.)
+                const bool red = (int)(((M == 1 ? 4 : 2) * p.q - qJ) >> 32) < 0; // uniform
                 // the first phase's twiddles as scalar loads (fwd_first_phase_s), issued with the prime's
                 // setup
-                fwd_first_phase_s<E, LOGE>(ar, v, reinterpret_cast<const char *>(tw_all + ((size_t)pi << log_n)) + twd);
+                fwd_first_phase_s<E, LOGE>(ar, v, xd, red, reinterpret_cast<const char *>(tw_all + ((size_t)pi << log_n)) + twd);
             }
             else if (twl_on)
             {
@@ -1237,22 +1284,40 @@ __global__ __launch_bounds__(256, (FP && !MIX) ? MHE_MODUP_OCC : MHE_MODUP_OCC_I
 #pragma unroll
                 for (int e = 0; e < E; e++) v[e] = lds_v[sl * LD + E * t + e];
             }
+            // a lazy prime's last stage is taken apart from the others: with `fold` it reduces x as the
+            // non-lazy butterfly does, so |x'|, |y'| <= 2q + 1 < 2^47 (q < 2^46) fit the packed slot
+            // with no reduction of their own
+            constexpr int S_END = M == 1 ? LOGR - 1 : LOGR;
             if (twl_on)
             {
 #pragma unroll
-                for (int s = LOGE; s < LOGR; s++)
+                for (int s = LOGE; s < S_END; s++)
                     ar.template fwd_tab<E>(v, 1 << (LOGR - 1 - s), tl,
                                            [&](int e) { return (1 << s) + ((E * t + e) >> (LOGR - s)); });
             }
             else
             {
 #pragma unroll
-                for (int s = LOGE; s < LOGR; s++)
+                for (int s = LOGE; s < S_END; s++)
                     ar.template fwd<E>(v, 1 << (LOGR - 1 - s),
                                        [&](int e) { return (1 << s) + ((E * t + e) >> (LOGR - s)); });
             }
+            if constexpr (M == 1)
+            {
+                auto ix = [&](int e) { return (1 << (LOGR - 1)) + ((E * t + e) >> 1); };
+                if (fold)
+                {
+                    if (twl_on) ar.template fwd_tab_full<E>(v, 1, tl, ix);
+                    else ar.template fwd_full<E>(v, 1, ix);
+                }
+                else
+                {
+                    if (twl_on) ar.template fwd_tab<E>(v, 1, tl, ix);
+                    else ar.template fwd<E>(v, 1, ix);
+                }
+            }
             u64 *dst = modup + (((size_t)(I - I0) * L + J) << log_n);
-            if (inter_packed(pack, p.q)) // uniform per workgroup
+            if (packed) // uniform per workgroup
             {
                 // n = 2^16 here, so logC = 16 - LOGR is a constant and the tile offsets fold into
                 // one base per lane plus immediates
@@ -1260,31 +1325,41 @@ __global__ __launch_bounds__(256, (FP && !MIX) ? MHE_MODUP_OCC : MHE_MODUP_OCC_I
                 u32 *lo = reinterpret_cast<u32 *>(dst) + tile16(c + ((u32)(E * t) << LC));
                 // word index of the lane's first row pair (E t is a multiple of 16: tile16h is even)
                 u32 *hi = reinterpret_cast<u32 *>(dst) + 65536 + (tile16h(c + ((u32)(E * t) << LC)) >> 1);
+                auto emit = [&](auto folded) {
 #pragma unroll
-                for (int e = 0; e < E; e += 2)
-                {
-                    // FP: the centred residue as 48-bit two's complement (fp_to_s48; k_ks_row_mac
-                    // reads it back with fp_from_s48); integer: the canonical residue
-                    u64 o0, o1;
-                    if constexpr (M != 0)
+                    for (int e = 0; e < E; e += 2)
                     {
-                        o0 = fp_to_s48(v[e], ar.q, ar.qinv);
-                        o1 = fp_to_s48(v[e + 1], ar.q, ar.qinv);
+                        // FP: the centred residue as 48-bit two's complement (fp_to_s48; k_ks_row_mac
+                        // reads it back with fp_from_s48), or with `fold` the last stage's output as it
+                        // stands (fp_s48_of); integer: the canonical residue
+                        u64 o0, o1;
+                        if constexpr (M != 0 && decltype(folded)::value)
+                        {
+                            o0 = fp_s48_of(v[e]);
+                            o1 = fp_s48_of(v[e + 1]);
+                        }
+                        else if constexpr (M != 0)
+                        {
+                            o0 = fp_to_s48(v[e], ar.q, ar.qinv);
+                            o1 = fp_to_s48(v[e + 1], ar.q, ar.qinv);
+                        }
+                        else
+                        {
+                            o0 = ar.out(v[e]);
+                            o1 = ar.out(v[e + 1]);
+                        }
+                        // tile16(c + ((E t + e) << LC)) - tile16(c + ((E t) << LC)), E t a multiple of 16
+                        const u32 k0 = ((u32)(e >> 4) << 12) | ((u32)(e & 15) << 4);
+                        const u32 k1 = ((u32)((e + 1) >> 4) << 12) | ((u32)((e + 1) & 15) << 4);
+                        st_nt<0>(&lo[k0], (u32)o0);
+                        st_nt<0>(&lo[k1], (u32)o1);
+                        // the same difference for tile16h in words: row pair (e & 15) / 2 of tile row e / 16
+                        const u32 kw = ((u32)(e >> 4) << 11) | ((u32)((e & 15) >> 1) << 4);
+                        st_nt<0>(&hi[kw], ((u32)(o0 >> 32) & 0xFFFFu) | ((u32)(o1 >> 32) << 16));
                     }
-                    else
-                    {
-                        o0 = ar.out(v[e]);
-                        o1 = ar.out(v[e + 1]);
-                    }
-                    // tile16(c + ((E t + e) << LC)) - tile16(c + ((E t) << LC)), E t a multiple of 16
-                    const u32 k0 = ((u32)(e >> 4) << 12) | ((u32)(e & 15) << 4);
-                    const u32 k1 = ((u32)((e + 1) >> 4) << 12) | ((u32)((e + 1) & 15) << 4);
-                    st_nt<0>(&lo[k0], (u32)o0);
-                    st_nt<0>(&lo[k1], (u32)o1);
-                    // the same difference for tile16h in words: row pair (e & 15) / 2 of tile row e / 16
-                    const u32 kw = ((u32)(e >> 4) << 11) | ((u32)((e & 15) >> 1) << 4);
-                    st_nt<0>(&hi[kw], ((u32)(o0 >> 32) & 0xFFFFu) | ((u32)(o1 >> 32) << 16));
-                }
+                };
+                if (fold) emit(std::true_type{});
+                else emit(std::false_type{});
             }
             else
             {
@@ -1292,8 +1367,25 @@ __global__ __launch_bounds__(256, (FP && !MIX) ? MHE_MODUP_OCC : MHE_MODUP_OCC_I
                 // keep (they were spilled to scratch and reloaded with a vmcnt(0) wait per store)
                 const size_t stride = (size_t)1 << logC;
                 u64 *d0 = dst + c + ((size_t)(E * t) << logC);
+                if (f64)
+                {
+                    // MHE_INTER_F64: the double itself, for the fused MAC's FP path -- the last
+                    // non-lazy butterfly's output (|v| <= 2q + 1, what that path's row stages take
+                    // between stages), or a lazy prime's centred residue
 #pragma unroll
-                for (int e = 0; e < E; e++) st_nt<0>(d0 + (size_t)e * stride, ar.out(v[e]));
+                    for (int e = 0; e < E; e++)
+                    {
+                        double o = 0;
+                        if constexpr (M == 2) o = v[e];
+                        if constexpr (M == 1) o = fp_reduce(v[e], ar.q, ar.qinv);
+                        st_nt<0>(d0 + (size_t)e * stride, (u64)__double_as_longlong(o));
+                    }
+                }
+                else
+                {
+#pragma unroll
+                    for (int e = 0; e < E; e++) st_nt<0>(d0 + (size_t)e * stride, ar.out(v[e]));
+                }
             }
             if constexpr (!PG) lds_barrier(); // lds is rewritten by the next output prime (its stores need not land)
         }
@@ -1322,26 +1414,26 @@ static inline void modup_col_a(const KsPtrs &P, int B, const PrimeDev *primes, c
 }
 
 // ModUp column pass for output primes I0 .. I0+Icnt-1 (each entry's inter holds exactly those), in
-// IG groups of output primes per digit, over B batch entries.  pack (n = 2^16 only): limbs of
+// IG groups of output primes per digit, over B batch entries.  pack bit 0 (n = 2^16 only): limbs of
 // primes below 2^48 are stored in the packed 48-bit form (tile16), which k_ks_row_mac must then be
-// told as well.
+// told as well; bit 1 (MHE_INTER_F64, any n): the FP sweeps' other limbs as doubles, for that kernel.
 static inline void modup_col(const KsPtrs &P, int B, const PrimeDev *primes, const Tw *tw, int L, int K,
                              int log_n, const NttMode &m, int I0, int Icnt, int IG, int pack, hipStream_t st)
 {
     switch ((log_n + 1) / 2)
     {
     case 6:
-        if (m.fp == 2) modup_col_a<6, true, true>(P, B, primes, tw, L, K, log_n, m.dfwd, I0, Icnt, IG, 0, st);
-        else if (m.fp) modup_col_a<6, true>(P, B, primes, tw, L, K, log_n, m.dfwd, I0, Icnt, IG, 0, st);
-        else modup_col_a<6, false>(P, B, primes, tw, L, K, log_n, 0, I0, Icnt, IG, 0, st);
+        if (m.fp == 2) modup_col_a<6, true, true>(P, B, primes, tw, L, K, log_n, m.dfwd, I0, Icnt, IG, pack & MHE_INTER_F64, st);
+        else if (m.fp) modup_col_a<6, true>(P, B, primes, tw, L, K, log_n, m.dfwd, I0, Icnt, IG, pack & MHE_INTER_F64, st);
+        else modup_col_a<6, false>(P, B, primes, tw, L, K, log_n, 0, I0, Icnt, IG, pack & MHE_INTER_F64, st);
         break;
     case 7:
-        if (m.fp == 2) modup_col_a<7, true, true>(P, B, primes, tw, L, K, log_n, m.dfwd, I0, Icnt, IG, 0, st);
-        else if (m.fp) modup_col_a<7, true>(P, B, primes, tw, L, K, log_n, m.dfwd, I0, Icnt, IG, 0, st);
-        else modup_col_a<7, false>(P, B, primes, tw, L, K, log_n, 0, I0, Icnt, IG, 0, st);
+        if (m.fp == 2) modup_col_a<7, true, true>(P, B, primes, tw, L, K, log_n, m.dfwd, I0, Icnt, IG, pack & MHE_INTER_F64, st);
+        else if (m.fp) modup_col_a<7, true>(P, B, primes, tw, L, K, log_n, m.dfwd, I0, Icnt, IG, pack & MHE_INTER_F64, st);
+        else modup_col_a<7, false>(P, B, primes, tw, L, K, log_n, 0, I0, Icnt, IG, pack & MHE_INTER_F64, st);
         break;
     case 8:
-        pack = (pack && log_n == 16) ? 1 : 0;
+        pack = (((pack & 1) && log_n == 16) ? 1 : 0) | (pack & MHE_INTER_F64);
         if (m.fp == 2) modup_col_a<8, true, true>(P, B, primes, tw, L, K, log_n, m.dfwd, I0, Icnt, IG, pack, st);
         else if (m.fp) modup_col_a<8, true>(P, B, primes, tw, L, K, log_n, m.dfwd, I0, Icnt, IG, pack, st);
         else modup_col_a<8, false>(P, B, primes, tw, L, K, log_n, 0, I0, Icnt, IG, pack, st);
@@ -1714,13 +1806,15 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8 && NE == 1) ? MHE_KS_
         const bool has_self = I < L;                                                 // uniform
         const int nd = has_self ? L - 1 : L; // digits other than I
         auto loop = [&](auto pk_c, auto kf_c) {
-            constexpr bool PK = decltype(pk_c)::value;
+            constexpr int IF = decltype(pk_c)::value; // digit slots: 0 canonical, 1 packed, 2 doubles
+            constexpr bool PK = IF == 1;
             constexpr int KF = decltype(kf_c)::value; // key slot format (key_slot_format)
             auto digit_of = [&](int u) { return u + ((has_self && u >= I) ? 1 : 0); };
             // packed digit slots at n = 2^16: byte offsets of this lane's residue 0 in the 32-bit
             // plane and in the 16-bit plane (which starts at 4n)
             const u32 off_lo = 4u * tile16(base + lay(t, 0, B_A));
             const u32 off_hi = 4u * (u32)n + 2u * tile16h(base + lay(t, 0, B_A));
+            const u32 off_f64 = 8u * (base + lay(t, 0, B_A)); // slots of doubles: residue 0's byte offset
             auto load_inter = [&](int x, int J, u64 (&v)[8]) {
                 if constexpr (PK && LOGR == 8)
                 {
@@ -1739,6 +1833,21 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8 && NE == 1) ? MHE_KS_
                         const u32 l = __builtin_amdgcn_raw_buffer_load_b32(rs, (int)off_lo, 2048 * e, AUX);
                         const u32 h = __builtin_amdgcn_raw_buffer_load_b16(rs, (int)off_hi, 1024 * e, AUX);
                         v[e] = (u64)l | ((u64)h << 32);
+                    }
+                }
+                else if constexpr (IF == 2 && LOGR == 8)
+                {
+                    // the same for a slot of doubles: one lane offset, residue e at 8 (e << B_A) bytes
+                    const u64 *slot = inter[x] + ((size_t)(I - I0) * L + J) * n;
+                    const __amdgpu_buffer_rsrc_t rs =
+                        __builtin_amdgcn_make_buffer_rsrc(const_cast<u64 *>(slot), 0, (int)(8 * n), 0x00020000);
+                    constexpr int AUX = ((MHE_NT >> 2) & 1) ? 2 : 0; // nt
+                    typedef u32 u32x2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+                    for (int e = 0; e < 8; e++)
+                    {
+                        const u32x2 r = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)off_f64, (8 << B_A) * e, AUX);
+                        v[e] = (u64)r.x | ((u64)r.y << 32);
                     }
                 }
                 else if constexpr (PK)
@@ -1834,9 +1943,12 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8 && NE == 1) ? MHE_KS_
 #pragma unroll
                     for (int e = 0; e < 8; e++)
                     {
-                        // the column-pass output: FP and packed, a centred 48-bit residue (fp_to_s48);
-                        // otherwise canonical
-                        if constexpr (FPA)
+                        // the column-pass output: FP and packed, a signed 48-bit residue (fp_to_s48 or
+                        // fp_s48_of: |w| <= 2q + 1, inside what either butterfly takes); FP with
+                        // MHE_INTER_F64, the double itself (|w| <= 2q + 1 as well); otherwise canonical
+                        if constexpr (FPA && IF == 2)
+                            w[x][e] = __longlong_as_double((long long)vin[x][e]);
+                        else if constexpr (FPA)
                             w[x][e] = PK ? fp_from_s48(vin[x][e]) : ar.in52(vin[x][e]);
                         else
                             w[x][e] = ar.in52(vin[x][e]);
@@ -1946,18 +2058,17 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8 && NE == 1) ? MHE_KS_
         using F0 = std::integral_constant<int, 0>;
         using F1 = std::integral_constant<int, 1>;
         using F2 = std::integral_constant<int, 2>;
+        auto loops = [&](auto if_c) {
+            if (kfmt == 1) loop(if_c, F1{});
+            else if (kfmt == 2) loop(if_c, F2{});
+            else loop(if_c, F0{});
+        };
+        // a non-packed slot of the FP arithmetic holds doubles (MHE_INTER_F64): always, so that the
+        // kernel has no third set of loops (with one, NE = 2 spilled 167 VGPRs and NE = 1 127)
         if (pk)
-        {
-            if (kfmt == 1) loop(std::true_type{}, F1{});
-            else if (kfmt == 2) loop(std::true_type{}, F2{});
-            else loop(std::true_type{}, F0{});
-        }
+            loops(F1{});
         else
-        {
-            if (kfmt == 1) loop(std::false_type{}, F1{});
-            else if (kfmt == 2) loop(std::false_type{}, F2{});
-            else loop(std::false_type{}, F0{});
-        }
+            loops(std::integral_constant<int, FPA ? 2 : 0>{});
         // the epilogue, entry by entry (NE = 2: the second entry's after the first's; its share of
         // the kernel is small and the values of one entry at a time keep the registers low)
         auto finish = [&](auto xc) {
@@ -2158,7 +2269,8 @@ static inline int ks_row_mac_m(const KsPtrs &P, int B, const PrimeDev *primes, c
 }
 
 // Fused row pass + MAC for output primes I0 .. I0+cnt-1 (each entry's inter holds exactly those),
-// over B batch entries; share: every entry's key pointer is the same (XCD-grouped entries, and at
+// over B batch entries (a non-packed limb of a prime below 2^51 as doubles when the launch runs FP64:
+// MHE_INTER_F64); share: every entry's key pointer is the same (XCD-grouped entries, and at
 // n = 2^16 in FP64 two entries per workgroup: pr, ks_row_mac_a)
 // inv_special: the launch covers the special prime (I = L) and may finish the special limbs' inverse
 // row pass itself (itw: inverse twiddles); returns 1 when it did, 0 when k_inv_row must still run.
@@ -2171,7 +2283,7 @@ static inline int ks_row_mac_chunk(const KsPtrs &P, int B, const PrimeDev *prime
     case 6: return ks_row_mac_m<6>(P, B, primes, tw, L, K, log_n, m, I0, cnt, 0, kpack, share, pr, itw, inv_special, st);
     case 7: return ks_row_mac_m<7>(P, B, primes, tw, L, K, log_n, m, I0, cnt, 0, kpack, share, pr, itw, inv_special, st);
     case 8:
-        return ks_row_mac_m<8>(P, B, primes, tw, L, K, log_n, m, I0, cnt, (pack && log_n == 16) ? 1 : 0, kpack, share,
+        return ks_row_mac_m<8>(P, B, primes, tw, L, K, log_n, m, I0, cnt, ((pack & 1) && log_n == 16) ? 1 : 0, kpack, share,
                                pr, itw, inv_special, st);
     }
     return 0;

@@ -302,6 +302,7 @@ static int run_galois_hoisted(mhe_ctx *c, const u64 *const *in, int H, int count
     // 3. per MHE_MAXB rotations: c0 / c1 permuted into out, the classic ModUp + MAC of flagged
     //    inputs (their kernels return at once otherwise), the ModDown (c1 written)
     const int pack = (c->ks_pack && c->ks_colgroups > 0) ? 1 : 0;
+    const int pack_col = pack | MHE_INTER_F64; // the column pass in front of the fused MAC (ntt.h)
     std::vector<int> order(count);
     for (int i = 0; i < count; i++) order[i] = i;
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return keys[a] < keys[b]; });
@@ -331,7 +332,7 @@ static int run_galois_hoisted(mhe_ctx *c, const u64 *const *in, int H, int count
         count_op(c, MHE_OPK_KEYSWITCH, L, (unsigned long long)B);
         intt_targets(c, w, c1, B, L, flagged, st);
         const KsPtrs kp = ks_ptrs(w, jobs, B, accs, flagged);
-        modup_col(kp, B, c->primes, c->tw, L, c->K, log_n, c->nm_ks, 0, L + 1, IG, pack, st);
+        modup_col(kp, B, c->primes, c->tw, L, c->K, log_n, c->nm_ks, 0, L + 1, IG, pack_col, st);
         ks_row_mac_chunk(kp, B, c->primes, c->tw, L, c->K, log_n, c->nm_ks, 0, L + 1, pack, kpack, ks_shared_key(c, jobs, B),
                          ks_pair_of(c), c->itw, 0, st);
         HIP_LAUNCH_CHECK();
