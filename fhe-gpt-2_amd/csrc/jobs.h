@@ -1,7 +1,7 @@
 // Job descriptors of the NTT passes (ntt.h): a job maps the launch's job index y to a view -- the
 // source and destination of one limb, its prime and twiddles, and the load / store that fuse the
 // step's arithmetic (lifts, epilogues) into the transform.  Kernel arguments, filled on the host by
-// the pipelines of keyswitch.h and rotate.h.
+// the pipelines of keyswitch.h, rotate.h and prodsum.h.
 #pragma once
 
 // A batch of jobs of one kind: entry e owns job indices [e * per, (e + 1) * per) of the launch and
@@ -10,13 +10,86 @@ template <class Job>
 struct JobB
 {
     Job j[MHE_MAXB];
-    int per = 1; // jobs per entry
+    int per; // jobs per entry
+    explicit JobB(int per_) : per(per_) {}
     __device__ auto view(int y) const
     {
         const int e = y / per;
         return j[e].view(y - e * per);
     }
 };
+// The ModDown lift (evaluator.cpp:2466-2524) of the special limb to prime p = q_i, with its constants.
+struct ModDownLift
+{
+    PrimeDev P;
+    u64 half, fix;
+    bool reduce;
+    __device__ u64 lift(u64 s, const PrimeDev &p) const // s in [0, 2P) -> [0, 2p)
+    {
+        u64 t = barrett64(s + half, P);
+        if (reduce) t = barrett64(t, p);
+        return t + fix;
+    }
+    // the integer lift() stands for, from s canonical mod P: s - P when s > P/2, else s
+    __device__ double lift_c(u64 s) const { return fp_from_u52(s) - (s > half ? (double)P.q : 0.0); }
+};
+__device__ __forceinline__ ModDownLift moddown_lift(const PrimeDev *primes, int i, int K)
+{
+    const PrimeDev p = prime_at(primes, i), P = prime_at(primes, K - 1);
+    return ModDownLift{ P, P.q >> 1, p.q - barrett64(P.q >> 1, p), P.q > p.q };
+}
+
+// The rescale lift (util/rns.cpp:737-808) of the last limb (prime q_last = q_{L-1}) to prime p = q_i.
+struct RescaleLift
+{
+    u64 ql, half, neg_half;
+    bool reduce;
+    // lift(s) = finish(shift(s)): s canonical mod q_last -> [0, 2p)
+    __device__ u64 shift(u64 s) const { return csub(s + half, ql); }
+    __device__ u64 finish(u64 v, const PrimeDev &p) const
+    {
+        if (reduce) v = barrett64(v, p);
+        return v + neg_half;
+    }
+    __device__ u64 lift(u64 s, const PrimeDev &p) const { return finish(shift(s), p); }
+    // the integer lift() stands for: s - q_last when s > q_last/2, else s
+    __device__ double lift_c(u64 s) const { return fp_from_u52(s) - (s > half ? (double)ql : 0.0); }
+};
+__device__ __forceinline__ RescaleLift rescale_lift(const PrimeDev *primes, int i, int L)
+{
+    const PrimeDev p = prime_at(primes, i);
+    const u64 ql = prime_at(primes, L - 1).q;
+    return RescaleLift{ ql, ql >> 1, p.q - barrett64(ql >> 1, p), p.q < ql };
+}
+
+// The view of a column pass that lifts one source limb to prime p and starts its NTT (ntt.h: k_fwd_col
+// loads through lift(), k_icol_lift calls lift() or lift_c() on its own inverse pass's output).
+template <class Lift>
+struct LiftColView
+{
+    const u64 *src;
+    u64 *dst;
+    PrimeDev p;
+    Lift lf;
+    const Tw *tw;
+    bool skip;
+    __device__ u64 lift(u64 s) const { return lf.lift(s, p); }
+    __device__ double lift_c(u64 s) const { return lf.lift_c(s); }
+    __device__ u64 load(u32 x) const { return lift(src[x]); }
+    __device__ void store(u32 x, u64 v) const { dst[x] = v; }
+};
+
+// The FP64 constants of a prime (fparith.h): q and 1/q.
+struct PrimeF
+{
+    double pd, pi;
+};
+__device__ __forceinline__ PrimeF prime_f(const PrimeDev &p)
+{
+    const double pd = (double)p.q;
+    return PrimeF{ pd, 1.0 / pd };
+}
+
 // Plain transform over [poly][limb][n] with limb l on prime l (optionally src != dst).
 struct JobPlain
 {
@@ -199,41 +272,13 @@ struct JobModDownCol
     const Tw *tw;
     int L, K, log_n;
     int fixed_i = -1; // >= 0: one job per poly, all on limb fixed_i
-    struct View
-    {
-        const u64 *src;
-        u64 *dst;
-        PrimeDev p;
-        PrimeDev P;
-        const Tw *tw;
-        u64 half, fix;
-        bool reduce;
-        bool skip;
-        __device__ u64 lift(u64 s) const
-        {
-            u64 t = barrett64(s + half, P);
-            if (reduce) t = barrett64(t, p);
-            return t + fix;
-        }
-        // the integer lift() stands for, from s canonical mod P: s - P when s > P/2, else s
-        __device__ double lift_c(u64 s) const { return fp_from_u52(s) - (s > half ? (double)P.q : 0.0); }
-        __device__ u64 load(u32 x) const { return lift(src[x]); }
-        __device__ void store(u32 x, u64 v) const { dst[x] = v; }
-    };
+    using View = LiftColView<ModDownLift>;
     __device__ View view(int y) const
     {
         const int k = fixed_i >= 0 ? y : y / L, i = fixed_i >= 0 ? fixed_i : y % L;
-        View v;
-        v.src = acc + ((size_t)(k * (L + 1) + L) << log_n);
-        v.dst = scratch + ((size_t)y << log_n);
-        v.p = prime_at(primes, i);
-        v.P = prime_at(primes, K - 1);
-        v.tw = tw + ((size_t)i << log_n);
-        v.half = v.P.q >> 1;
-        v.fix = v.p.q - barrett64(v.half, v.p);
-        v.reduce = v.P.q > v.p.q;
-        v.skip = false;
-        return v;
+        const Tw *twi = tw + ((size_t)i << log_n); // ahead of the lift's loads: the order the kernels keep
+        return View{ acc + ((size_t)(k * (L + 1) + L) << log_n), scratch + ((size_t)y << log_n), prime_at(primes, i),
+                     moddown_lift(primes, i, K), twi, false };
     }
 };
 
@@ -260,7 +305,8 @@ struct JobModDownRow
         bool skip;
         bool replace;
         bool fp;
-        double pd, pi, invd;
+        PrimeF f;
+        double invd;
         __device__ u64 load(u32 x) const { return buf[x]; }
         struct Pre
         {
@@ -273,8 +319,8 @@ struct JobModDownRow
             {
                 // acc and t canonical: (acc - t) P^-1 in (-1.25p, 1.25p), plus c < p, one
                 // canonicalisation (|.| < 2^53): the residue of the integer form
-                const double v = fp_mulmod_gen(fp_from_u52(o.a) - fp_from_u52(t), invd, pd, pi);
-                ctp[x] = fp_canon(replace ? v : v + fp_from_u52(o.c), pd, pi);
+                const double v = fp_mulmod_gen(fp_from_u52(o.a) - fp_from_u52(t), invd, f.pd, f.pi);
+                ctp[x] = fp_canon(replace ? v : v + fp_from_u52(o.c), f.pd, f.pi);
                 return;
             }
             u64 v = mul_shoup(o.a + p.four_q - t, inv.x, inv.y, p.q);
@@ -295,8 +341,7 @@ struct JobModDownRow
         v.skip = false;
         v.replace = c1_write && k == 1;
         v.fp = fp != 0;
-        v.pd = (double)v.p.q;
-        v.pi = 1.0 / v.pd;
+        v.f = prime_f(v.p);
         v.invd = (double)v.inv.x;
         return v;
     }
@@ -312,40 +357,12 @@ struct JobRescaleCol
     const PrimeDev *primes;
     const Tw *tw;
     int L, log_n;
-    struct View
-    {
-        const u64 *src;
-        u64 *dst;
-        PrimeDev p;
-        u64 ql, half, neg_half;
-        const Tw *tw;
-        bool reduce;
-        bool skip;
-        __device__ u64 lift(u64 s) const // s canonical mod q_last
-        {
-            u64 v = csub(s + half, ql);
-            if (reduce) v = barrett64(v, p);
-            return v + neg_half;
-        }
-        // the integer lift() stands for: s - q_last when s > q_last/2, else s
-        __device__ double lift_c(u64 s) const { return fp_from_u52(s) - (s > half ? (double)ql : 0.0); }
-        __device__ u64 load(u32 x) const { return lift(src[x]); }
-        __device__ void store(u32 x, u64 v) const { dst[x] = v; }
-    };
+    using View = LiftColView<RescaleLift>;
     __device__ View view(int y) const
     {
         const int s = y / (L - 1), i = y % (L - 1);
-        View v;
-        v.src = last + ((size_t)s << log_n);
-        v.dst = scratch + ((size_t)y << log_n);
-        v.p = prime_at(primes, i);
-        v.ql = prime_at(primes, L - 1).q;
-        v.half = v.ql >> 1;
-        v.neg_half = v.p.q - barrett64(v.half, v.p);
-        v.tw = tw + ((size_t)i << log_n);
-        v.reduce = v.p.q < v.ql;
-        v.skip = false;
-        return v;
+        return View{ last + ((size_t)s << log_n), scratch + ((size_t)y << log_n), prime_at(primes, i),
+                     rescale_lift(primes, i, L), tw + ((size_t)i << log_n), false };
     }
 };
 
@@ -368,14 +385,15 @@ struct JobRescaleRow
         const Tw *tw;
         Tw inv;
         bool skip, fp;
-        double pd, pi, invd;
+        PrimeF f;
+        double invd;
         __device__ u64 load(u32 x) const { return buf[x]; }
         using Pre = u64;
         __device__ Pre pre(u32 x) const { return inp[x]; }
         __device__ void store(u32 x, u64 t, u64 in) const
         {
             if (fp) // in and t canonical: (in - t) q_last^-1 in (-1.25p, 1.25p), canonicalised
-                outp[x] = fp_canon(fp_mulmod_gen(fp_from_u52(in) - fp_from_u52(t), invd, pd, pi), pd, pi);
+                outp[x] = fp_canon(fp_mulmod_gen(fp_from_u52(in) - fp_from_u52(t), invd, f.pd, f.pi), f.pd, f.pi);
             else
                 outp[x] = mul_shoup(in + p.four_q - t, inv.x, inv.y, p.q);
         }
@@ -393,8 +411,7 @@ struct JobRescaleRow
         v.inv = tw_at(invq, (size_t)(L - 1) * K + i);
         v.skip = false;
         v.fp = fp != 0;
-        v.pd = (double)v.p.q;
-        v.pi = 1.0 / v.pd;
+        v.f = prime_f(v.p);
         v.invd = (double)v.inv.x;
         return v;
     }
@@ -427,7 +444,8 @@ struct JobMDRCol
         Tw pinv;
         u64 halfP, fixP, ql, halfL, neg_halfL;
         bool redP, redL, skip, fp;
-        double pd, pi, pinvd;
+        PrimeF f;
+        double pinvd;
         __device__ u64 load(u32 x) const
         {
             if (fp)
@@ -437,8 +455,8 @@ struct JobMDRCol
                 // P^-1 is in (-2p, 2p), the sum below 2^53: one canonicalisation, the same residue
                 const u64 t = csub(csub(accP[x] + halfP, 2 * P.q), P.q);
                 const u64 r = csub(lastp[x] + halfL, ql);
-                const double u = fp_mulmod_gen(fp_from_u52(t + fixP), pinvd, pd, pi) + fp_from_u52(r + neg_halfL);
-                return fp_canon(u, pd, pi);
+                const double u = fp_mulmod_gen(fp_from_u52(t + fixP), pinvd, f.pd, f.pi) + fp_from_u52(r + neg_halfL);
+                return fp_canon(u, f.pd, f.pi);
             }
             u64 t = barrett64(accP[x] + halfP, P);
             if (redP) t = barrett64(t, p);
@@ -459,7 +477,7 @@ struct JobMDRCol
             cr = fp_from_u52(l) - (l > halfL ? (double)ql : 0.0);
         }
         // t P^-1 + r mod p from them: |.| < 1.25p + 2^50, congruent to load()'s value
-        __device__ double lift_f(double ct, double cr) const { return fp_mulmod_gen(ct, pinvd, pd, pi) + cr; }
+        __device__ double lift_f(double ct, double cr) const { return fp_mulmod_gen(ct, pinvd, f.pd, f.pi) + cr; }
     };
     __device__ View view(int y) const
     {
@@ -481,8 +499,7 @@ struct JobMDRCol
         v.redL = v.p.q < v.ql;
         v.skip = false;
         v.fp = fp != 0;
-        v.pd = (double)v.p.q;
-        v.pi = 1.0 / v.pd;
+        v.f = prime_f(v.p);
         v.pinvd = (double)v.pinv.x;
         return v;
     }
@@ -508,7 +525,8 @@ struct JobMDRRow
         const Tw *tw;
         Tw pinv, qlinv;
         bool skip, fp;
-        double pd, pi, pinvd, qlinvd;
+        PrimeF f;
+        double pinvd, qlinvd;
         __device__ u64 load(u32 x) const { return buf[x]; }
         struct Pre
         {
@@ -521,9 +539,9 @@ struct JobMDRRow
             {
                 // acc_i P^-1 in (-1.25p, 1.25p); c + a - U is an exact integer below 2^53; its
                 // centered residue times q_{L-1}^-1, canonicalised: the residue of the integer form
-                const double a = fp_mulmod_gen(fp_from_u52(o.a), pinvd, pd, pi);
-                const double v = fp_reduce(fp_from_u52(o.c) + a - fp_from_u52(U), pd, pi);
-                outp[x] = fp_canon(fp_mulmod_gen(v, qlinvd, pd, pi), pd, pi);
+                const double a = fp_mulmod_gen(fp_from_u52(o.a), pinvd, f.pd, f.pi);
+                const double v = fp_reduce(fp_from_u52(o.c) + a - fp_from_u52(U), f.pd, f.pi);
+                outp[x] = fp_canon(fp_mulmod_gen(v, qlinvd, f.pd, f.pi), f.pd, f.pi);
                 return;
             }
             const u64 a = mul_shoup(o.a, pinv.x, pinv.y, p.q); // acc_i P^-1
@@ -546,8 +564,7 @@ struct JobMDRRow
         v.qlinv = tw_at(invq, (size_t)(L - 1) * K + i);
         v.skip = false;
         v.fp = fp != 0;
-        v.pd = (double)v.p.q;
-        v.pi = 1.0 / v.pd;
+        v.f = prime_f(v.p);
         v.pinvd = (double)v.pinv.x;
         v.qlinvd = (double)v.qlinv.x;
         return v;
@@ -574,24 +591,23 @@ struct JobProdSumCol
         const u64 *Tp, *lastp;
         u64 *dst;
         PrimeDev p;
+        RescaleLift rs;
         const Tw *tw;
         Tw pinv;
-        u64 ql, halfL, neg_halfL;
-        bool redL, skip, fp;
-        double pd, pi, pinvd;
+        bool skip, fp;
+        PrimeF f;
+        double pinvd;
         __device__ u64 load(u32 x) const
         {
+            u64 r = rs.shift(lastp[x]); // above the branch: the order the kernels keep
             if (fp)
             {
-                // T canonical and the rescale lift r + neg_halfL are exact doubles (< 2^52), the
+                // T canonical and the rescale lift r + neg_half are exact doubles (< 2^52), the
                 // product by P^-1 is in (-1.25p, 1.25p), the sum below 2^53: one canonicalisation
-                const u64 r = csub(lastp[x] + halfL, ql);
-                const double u = fp_mulmod_gen(fp_from_u52(Tp[x]), pinvd, pd, pi) + fp_from_u52(r + neg_halfL);
-                return fp_canon(u, pd, pi);
+                const double u = fp_mulmod_gen(fp_from_u52(Tp[x]), pinvd, f.pd, f.pi) + fp_from_u52(r + rs.neg_half);
+                return fp_canon(u, f.pd, f.pi);
             }
-            u64 r = csub(lastp[x] + halfL, ql);
-            if (redL) r = barrett64(r, p);
-            r += neg_halfL;                                          // rescale lift, [0, 2q)
+            r = rs.finish(r, p);                                     // rescale lift, [0, 2q)
             const u64 u = mul_shoup(Tp[x], pinv.x, pinv.y, p.q) + r; // [0, 3q)
             return csub(csub(u, p.two_q), p.q);
         }
@@ -607,14 +623,10 @@ struct JobProdSumCol
         v.p = prime_at(primes, i);
         v.tw = tw + ((size_t)i << log_n);
         v.pinv = tw_at(invq, (size_t)(K - 1) * K + i);
-        v.ql = prime_at(primes, L - 1).q;
-        v.halfL = v.ql >> 1;
-        v.neg_halfL = v.p.q - barrett64(v.halfL, v.p);
-        v.redL = v.p.q < v.ql;
+        v.rs = rescale_lift(primes, i, L);
         v.skip = false;
         v.fp = fp != 0;
-        v.pd = (double)v.p.q;
-        v.pi = 1.0 / v.pd;
+        v.f = prime_f(v.p);
         v.pinvd = (double)v.pinv.x;
         return v;
     }

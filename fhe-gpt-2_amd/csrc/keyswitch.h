@@ -87,8 +87,7 @@ static void intt_targets(mhe_ctx *c, Workspace *w, const u64 *const *src, int B,
                          hipStream_t st)
 {
     const size_t n = c->n;
-    JobB<JobStrided> j;
-    j.per = L;
+    JobB<JobStrided> j(L);
     for (int e = 0; e < B; e++)
         j.j[e] = JobStrided{ src[e], w->e[e].coeff, n, n, 0, 1, c->primes, c->itw, c->log_n, 0, run_if ? run_if[e] : nullptr };
     inv_row(j, c->log_n, B * L, c->nm, st);
@@ -133,6 +132,44 @@ static KsPair ks_pair_of(mhe_ctx *c)
     return KsPair{ c->ks_pair, &c->ks_paired, &c->ks_single };
 }
 
+// The fused HMult tail for B slots: with acc the key products (or their sum), ct the product's first
+// two polys (or their sum) and S = ct + ModDown(acc), the rescale of S to out [2][L-1][n].  Limb L-1
+// only: ct += (acc - NTT(t)) P^-1, t from col1's column pass into the slot's modup; last = INTT(S[L-1])
+// into its coeff; then limbs 0 .. L-2 through one forward NTT each, col2's column pass (modup = the
+// lifts of the special limbs and of last) and JobMDRRow.  ct limb L-1 is overwritten on the way.
+struct TailSlot
+{
+    const u64 *acc; // [2][L+1][n]
+    u64 *ct;        // [2][L][n]
+    u64 *out;       // [2][L-1][n]
+};
+
+template <class Col1, class Col2>
+static void run_hmult_tail(mhe_ctx *c, Workspace *w, const TailSlot *s, int B, int L, hipStream_t st, Col1 col1, Col2 col2)
+{
+    const int log_n = c->log_n, fp = c->nm.fp ? 1 : 0;
+    const size_t n = c->n;
+    JobB<JobModDownRow> dr(2);
+    JobB<JobLastInv> li(2);
+    JobB<JobStrided> j2(2);
+    JobB<JobMDRRow> mr(2 * (L - 1));
+    for (int e = 0; e < B; e++)
+    {
+        const WsEntry &we = w->e[e];
+        dr.j[e] = JobModDownRow{ we.modup, s[e].acc, s[e].ct, c->primes, c->tw, c->invq, L, c->K, log_n, L - 1 };
+        dr.j[e].fp = fp;
+        li.j[e] = JobLastInv{ s[e].ct, we.coeff, c->primes, c->itw, L, log_n, 1 };
+        j2.j[e] = JobStrided{ we.coeff, we.coeff, n, n, L - 1, 0, c->primes, c->itw, log_n, 1 };
+        mr.j[e] = JobMDRRow{ we.modup, s[e].acc, s[e].ct, s[e].out, c->primes, c->tw, c->invq, L, c->K, log_n, fp };
+    }
+    col1();
+    fwd_row(dr, log_n, 2 * B, c->nm, st);
+    inv_row(li, log_n, 2 * B, c->nm, st);
+    inv_col(j2, log_n, 2 * B, c->nm, st);
+    col2();
+    fwd_row(mr, log_n, 2 * (L - 1) * B, c->nm, st);
+}
+
 // Step 4 of a (batched) key switch, the ModDown (evaluator.cpp:2466-2524), over the key inner
 // products in w->e[e].acc (or accs[e]): ct_e += ModDown(acc_e), or with rescale_out the fused HMult tail (see
 // run_switch_key_batch).  special_inv_done: the key MAC already ran the special limbs' inverse
@@ -147,8 +184,7 @@ static void run_moddown(mhe_ctx *c, const KsJob *jobs, int B, int L, Workspace *
     const size_t n = c->n;
     // ModDown (evaluator.cpp:2466-2524): INTT_lazy of the special limbs, then fused
     //    lift + NTT + (c + 4q - t) * P^-1 + add.
-    JobB<JobStrided> j;
-    j.per = 2;
+    JobB<JobStrided> j(2);
     for (int e = 0; e < B; e++) j.j[e] = special_limbs(c, A(e), L);
     if (!special_inv_done) inv_row(j, log_n, 2 * B, c->nm, st);
     // the special limbs' inverse column pass runs inside the lift column pass (k_icol_lift)
@@ -164,10 +200,8 @@ static void run_moddown(mhe_ctx *c, const KsJob *jobs, int B, int L, Workspace *
     if (!fuse) inv_col(j, log_n, 2 * B, c->nm, st);
     if (!hm || L < 2)
     {
-        JobB<JobModDownCol> dc;
-        dc.per = 2 * L;
-        JobB<JobModDownRow> dr;
-        dr.per = 2 * L;
+        JobB<JobModDownCol> dc(2 * L);
+        JobB<JobModDownRow> dr(2 * L);
         for (int e = 0; e < B; e++)
         {
             dc.j[e] = JobModDownCol{ A(e), w->e[e].modup, c->primes, c->tw, L, c->K, log_n };
@@ -183,41 +217,26 @@ static void run_moddown(mhe_ctx *c, const KsJob *jobs, int B, int L, Workspace *
     }
     else
     {
-        // ModDown of limb L-1 only, its INTT (the rescale's "last"), then ModDown and
-        // rescale of the other limbs through one forward NTT each
-        JobB<JobModDownCol> dc;
-        dc.per = 2;
-        JobB<JobModDownRow> dr;
-        dr.per = 2;
-        JobB<JobLastInv> li;
-        li.per = 2;
-        JobB<JobStrided> j2;
-        j2.per = 2;
-        JobB<JobMDRCol> mc;
-        mc.per = 2 * (L - 1);
-        JobB<JobMDRRow> mr;
-        mr.per = 2 * (L - 1);
-        for (int e = 0; e < B; e++)
-        {
-            dc.j[e] = JobModDownCol{ A(e), w->e[e].modup, c->primes, c->tw, L, c->K, log_n, L - 1 };
-            dr.j[e] = JobModDownRow{ w->e[e].modup, A(e), jobs[e].ct, c->primes, c->tw, c->invq, L, c->K, log_n, L - 1 };
-            dr.j[e].fp = c->nm.fp ? 1 : 0;
-            li.j[e] = JobLastInv{ jobs[e].ct, w->e[e].coeff, c->primes, c->itw, L, log_n, 1 };
-            j2.j[e] = JobStrided{ w->e[e].coeff, w->e[e].coeff, n, n, L - 1, 0, c->primes, c->itw, log_n, 1 };
-            mc.j[e] = JobMDRCol{ A(e), w->e[e].coeff, w->e[e].modup, c->primes, c->tw, c->invq, L, c->K, log_n,
-                                 c->nm.fp ? 1 : 0 };
-            mr.j[e] = JobMDRRow{ w->e[e].modup, A(e), jobs[e].ct, jobs[e].rescale_out, c->primes, c->tw, c->invq,
-                                 L, c->K, log_n, c->nm.fp ? 1 : 0 };
-        }
-        fwd_col(dc, log_n, 2 * B, c->nm, st);
-        fwd_row(dr, log_n, 2 * B, c->nm, st);
-        inv_row(li, log_n, 2 * B, c->nm, st);
-        inv_col(j2, log_n, 2 * B, c->nm, st);
-        if (c->nm.fp == 1)
-            col_lift2(mc, 2 * B, L - 1, log_n, c->nm, st);
-        else
-            fwd_col(mc, log_n, 2 * (L - 1) * B, c->nm, st);
-        fwd_row(mr, log_n, 2 * (L - 1) * B, c->nm, st);
+        TailSlot ts[MHE_MAXB];
+        for (int e = 0; e < B; e++) ts[e] = TailSlot{ A(e), jobs[e].ct, jobs[e].rescale_out };
+        run_hmult_tail(
+            c, w, ts, B, L, st,
+            [&] {
+                JobB<JobModDownCol> dc(2);
+                for (int e = 0; e < B; e++)
+                    dc.j[e] = JobModDownCol{ A(e), w->e[e].modup, c->primes, c->tw, L, c->K, log_n, L - 1 };
+                fwd_col(dc, log_n, 2 * B, c->nm, st);
+            },
+            [&] {
+                JobB<JobMDRCol> mc(2 * (L - 1));
+                for (int e = 0; e < B; e++)
+                    mc.j[e] = JobMDRCol{ A(e), w->e[e].coeff, w->e[e].modup, c->primes, c->tw, c->invq, L, c->K, log_n,
+                                         c->nm.fp ? 1 : 0 };
+                if (c->nm.fp == 1)
+                    col_lift2(mc, 2 * B, L - 1, log_n, c->nm, st);
+                else
+                    fwd_col(mc, log_n, 2 * (L - 1) * B, c->nm, st);
+            });
     }
 }
 
@@ -282,8 +301,7 @@ static int run_switch_key_batch(mhe_ctx *c, const KsJob *jobs, int B, int L, hip
             modup_col(kp, B, c->primes, c->tw, L, c->K, log_n, c->nm_ks, 0, L + 1, std::min(c->ks_colgroups, L + 1), pack, st);
         else
         {
-            JobB<JobModUpCol> j;
-            j.per = (L + 1) * L;
+            JobB<JobModUpCol> j((L + 1) * L);
             // f64 follows nm_ks, the MAC's arithmetic (its reader), not nm, this pass's own: the store
             // converts a word below 2^52 whichever butterflies made it
             for (int e = 0; e < B; e++) j.j[e] = JobModUpCol{ w->e[e].coeff, w->e[e].modup, c->primes, c->tw, L, c->K, log_n, 0, c->nm_ks.fp ? 1 : 0 };
@@ -338,12 +356,9 @@ static int run_rescale_batch(mhe_ctx *c, const u64 *const *in, u64 *const *out, 
     count_op(c, MHE_OPK_RESCALE, L, (unsigned long long)B * size);
     const int log_n = c->log_n;
     // last[s] = INTT(in[s][L-1]) canonical -> the entry's coeff (size <= 3 polys)
-    JobB<JobLastInv> li;
-    li.per = size;
-    JobB<JobRescaleCol> rc;
-    rc.per = size * (L - 1);
-    JobB<JobRescaleRow> rr;
-    rr.per = size * (L - 1);
+    JobB<JobLastInv> li(size);
+    JobB<JobRescaleCol> rc(size * (L - 1));
+    JobB<JobRescaleRow> rr(size * (L - 1));
     ColSrc cs{};
     cs.stride = c->n;
     cs.per = size;
@@ -366,8 +381,7 @@ static int run_rescale_batch(mhe_ctx *c, const u64 *const *in, u64 *const *out, 
     }
     else
     {
-        JobB<JobStrided> j2;
-        j2.per = size;
+        JobB<JobStrided> j2(size);
         for (int e = 0; e < B; e++) j2.j[e] = JobStrided{ w->e[e].coeff, w->e[e].coeff, c->n, c->n, L - 1, 0, c->primes, c->itw, log_n, 1 };
         inv_col(j2, log_n, size * B, c->nm, st);
         fwd_col(rc, log_n, size * (L - 1) * B, c->nm, st);

@@ -199,6 +199,21 @@ struct Scratch
     }
 };
 
+// The group accumulators of a grouped sum (groupsum.h) for MHE_MAXB groups in flight at up to `limbs`
+// limbs, (words * limbs + 2) n words per group slot: the sum of the key products A [2][L+1][n], the sum
+// of the lifted special limbs T [2][L][n] and, with words = 6, the caller's own sum [2][L][n] behind them.
+// Allocated by the first call, grown when a call needs a higher level (get_groupsum).
+struct SumPool
+{
+    int words;
+    Scratch buf;
+    int limbs = 0;
+    u64 *at(int slot, int part, int L, size_t n) const // part 0: A, 1: T, 2: the caller's
+    {
+        return buf.p + ((size_t)slot * ((size_t)words * limbs + 2) + (part ? 2 * (L + 1) + 2 * L * (part - 1) : 0)) * n;
+    }
+};
+
 struct Workspace
 {
     int max_limbs = 0;
@@ -214,14 +229,8 @@ struct Workspace
     u64 *hoist[MHE_MAXB] = {};
     u64 *hacc[MHE_MAXB * MHE_HOIST_R] = {}; // [2][K][n] key products of each hoisted rotation
     int *flags = nullptr;
-    // mhe_rotate_sum: per group in flight (MHE_MAXB) the sum of the key products A [2][L+1][n] and the
-    // sum of the lifted special limbs T [2][L][n], L = rs_limbs; allocated by the first call
-    Scratch rs_base;
-    int rs_limbs = 0;
-    // mhe_relin_sum_rescale: per group in flight (MHE_MAXB) A [2][L+1][n], T [2][L][n] and the sum of
-    // the products' first two polys C [2][L][n], L = ps_limbs; allocated by the first call
-    Scratch ps_base;
-    int ps_limbs = 0;
+    SumPool rotsum{ 4 };  // mhe_rotate_sum: A and T
+    SumPool prodsum{ 6 }; // mhe_relin_sum_rescale: A, T and the sum C of the products' first two polys
     // kernel timing (mhe_ctx_set_timing): event pairs recorded around the two dominant
     // key-switch kernels on this stream, read back by mhe_kernel_time
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[2];
@@ -232,8 +241,8 @@ struct Workspace
     {
         base.release();
         hoist_base.release();
-        rs_base.release();
-        ps_base.release();
+        rotsum.buf.release();
+        prodsum.buf.release();
         if (flags) (void)hipFree(flags);
         flags = nullptr;
         for (auto &v : ev)
@@ -737,8 +746,7 @@ int mhe_internal_ntt_forward_entries(mhe_ctx *c, uint64_t *const *data, int B, i
 {
     if (B < 1 || B > MHE_MAXB) return fail(MHE_ERR_ARG, "forward NTT: batch size out of range");
     count_op(c, MHE_OPK_NTT, limbs, (unsigned long long)B);
-    JobB<JobFwdPlainIf> col, row;
-    col.per = row.per = limbs;
+    JobB<JobFwdPlainIf> col(limbs), row(limbs);
     for (int e = 0; e < B; e++)
     {
         const u32 *flag = skip_if ? skip_if + e : nullptr;
@@ -1200,7 +1208,7 @@ MHE_EXPORT int mhe_scratch_bytes(mhe_ctx *c, uint64_t *workspace, uint64_t *hois
         *workspace = *hoisting = 0;
         for (auto &kv : c->ws)
         {
-            *workspace += kv.second.base.bytes + kv.second.rs_base.bytes + kv.second.ps_base.bytes;
+            *workspace += kv.second.base.bytes + kv.second.rotsum.buf.bytes + kv.second.prodsum.buf.bytes;
             *hoisting += kv.second.hoist_base.bytes;
         }
         *streams = (int)c->ws.size();
@@ -1725,6 +1733,9 @@ MHE_EXPORT int mhe_apply_galois_to(mhe_ctx *c, const uint64_t *in, uint64_t *out
     HIP_TRY(hipMemsetAsync(out + ps, 0, ps * sizeof(u64), st));
     return run_switch_key(c, out, w->tmp, key, key_limbs, limbs, st);
 }
+
+// ------------------------------- what rotate-and-sum and relinearize-sum-rescale share
+#include "groupsum.h"
 
 // ------------------------------------------ batched rotations, hoisting and rotate-and-sum
 #include "rotate.h"

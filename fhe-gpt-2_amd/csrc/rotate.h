@@ -221,8 +221,7 @@ static int run_galois_hoisted(mhe_ctx *c, const u64 *const *in, int H, int count
         }
         modup_col(kp, H, c->primes, c->tw, L, c->K, log_n, c->nm_ks, 0, L + 1, IG, 0, st);
         auto row = [&](auto brev) {
-            JobB<JobModUpRowH<decltype(brev)::value>> rj;
-            rj.per = (L + 1) * L;
+            JobB<JobModUpRowH<decltype(brev)::value>> rj((L + 1) * L);
             for (int h = 0; h < H; h++) rj.j[h] = { w->e[h].modup, w->hoist[h], c->primes, c->tw, L, c->K, log_n };
             fwd_row(rj, log_n, H * (L + 1) * L, c->nm, st);
         };
@@ -492,94 +491,13 @@ MHE_EXPORT int mhe_ks_pair_stats(mhe_ctx *c, uint64_t *paired, uint64_t *single,
 }
 
 // ------------------------------------------------------------------------------ rotate and sum
-// mhe_rotate_sum: the key products of a chunk's entries folded into their groups' accumulators,
-// before the one ModDown forward NTT per limb of each group.  A chunk's entries come sorted by key
-// (they share the key stream of the MAC), so a group's entries are anywhere in it: zof[e] is the
-// chunk's group of entry e.  Every special limb has been through its own inverse NTT ([0, 2P)), so
-// each lift is SEAL's integer (evaluator.cpp:2466-2524) and the sums that follow are sums of
-// canonical residues mod q_i: the special limbs are never added mod P.
-struct RotSumPtrs
-{
-    const u64 *acc[MHE_MAXB];  // entry: key products [2][L+1][n], special limbs in coefficient form
-    const u64 *perm[MHE_MAXB]; // entry: permuted c0 [L][n]
-    u64 *A[MHE_MAXB];          // group: sum of the key products [2][L+1][n] (limbs 0 .. L-1 used)
-    u64 *T[MHE_MAXB];          // group: sum of the lifted special limbs [2][L][n], coefficient form
-    u64 *out[MHE_MAXB];        // group: out[0] += (or =) the permuted c0s
-    int zof[MHE_MAXB];         // entry: its group among the chunk's
-    int B;                     // entries in the chunk
-    int first[MHE_MAXB];       // group: its first chunk (A and T written, not added to)
-    int write0[MHE_MAXB];      // group: out[0] written, not added to (first chunk without accumulate)
-};
-
-// grid (n / 512, 2 * L, groups in the chunk); one lane owns two adjacent words of (group, k, i)
-__global__ __launch_bounds__(256) void k_rotsum_acc(RotSumPtrs P, const PrimeDev *__restrict__ primes, int L, int K,
-                                                    int log_n)
-{
-    const int z = blockIdx.z, k = blockIdx.y / L, i = blockIdx.y - k * L;
-    const size_t x = ((size_t)blockIdx.x * 256 + threadIdx.x) * 2;
-    const size_t n = (size_t)1 << log_n;
-    JobModDownCol::View v; // the ModDown column pass's lift, with its constants
-    v.p = prime_at(primes, i);
-    v.P = prime_at(primes, K - 1);
-    v.half = v.P.q >> 1;
-    v.fix = v.p.q - barrett64(v.half, v.p);
-    v.reduce = v.P.q > v.p.q;
-    const u64 q = v.p.q;
-    const size_t oa = (size_t)(k * (L + 1) + i) * n + x, os = (size_t)(k * (L + 1) + L) * n + x;
-    const size_t ot = (size_t)(k * L + i) * n + x, oc = (size_t)i * n + x;
-    ulonglong2 a{ 0, 0 }, t{ 0, 0 }, c0{ 0, 0 };
-    if (!P.first[z])
-    {
-        a = *(const ulonglong2 *)(P.A[z] + oa);
-        t = *(const ulonglong2 *)(P.T[z] + ot);
-    }
-    if (k == 0 && !P.write0[z]) c0 = *(const ulonglong2 *)(P.out[z] + oc);
-    for (int e = 0; e < P.B; e++)
-    {
-        if (P.zof[e] != z) continue; // uniform over the workgroup
-        const ulonglong2 ae = *(const ulonglong2 *)(P.acc[e] + oa);
-        const ulonglong2 se = *(const ulonglong2 *)(P.acc[e] + os);
-        a.x = addmod(a.x, ae.x, q);
-        a.y = addmod(a.y, ae.y, q);
-        t.x = addmod(t.x, csub(v.lift(se.x), q), q); // lift() is in [0, 2q)
-        t.y = addmod(t.y, csub(v.lift(se.y), q), q);
-        if (k == 0)
-        {
-            const ulonglong2 ce = *(const ulonglong2 *)(P.perm[e] + oc);
-            c0.x = addmod(c0.x, ce.x, q);
-            c0.y = addmod(c0.y, ce.y, q);
-        }
-    }
-    *(ulonglong2 *)(P.A[z] + oa) = a;
-    *(ulonglong2 *)(P.T[z] + ot) = t;
-    if (k == 0) *(ulonglong2 *)(P.out[z] + oc) = c0;
-}
-
-// The scratch of mhe_rotate_sum on stream st: the workspace for `entries` batch entries and the
-// accumulators of MHE_MAXB groups at L limbs (grown, after draining the stream, when a call needs a
-// higher level).
-static int get_rotsum(mhe_ctx *c, hipStream_t st, int entries, int L, Workspace **out)
-{
-    Workspace *w;
-    int r = get_ws(c, st, c->K - 1, &w, entries);
-    if (r) return r;
-    std::lock_guard<std::mutex> g(w->mu);
-    if (w->rs_limbs < L)
-    {
-        w->rs_limbs = 0;
-        if ((r = w->rs_base.grow(c, st, (size_t)MHE_MAXB * (4 * (size_t)L + 2) * c->n * sizeof(u64)))) return r;
-        w->rs_limbs = L;
-    }
-    *out = w;
-    return MHE_OK;
-}
-
+// mhe_rotate_sum: a grouped sum (groupsum.h) whose entry e is in[e] rotated by elts[e].  The key switch
+// of the permuted c1 leaves acc^e, the extra summand is the permuted c0, and its sum goes straight to
+// out[g][0].  A chunk's entries come sorted by key (they share the key stream of the MAC), so a
+// group's entries are anywhere in it.  One ModDown forward NTT per limb of each group follows.
 MHE_EXPORT int mhe_rotsum_stats(mhe_ctx *c, uint64_t *sums, uint64_t *terms, int reset)
 {
-    if (!valid_ctx(c) || !sums || !terms) return fail(MHE_ERR_ARG, "invalid argument");
-    *sums = reset ? c->rotsum_sums.exchange(0) : c->rotsum_sums.load();
-    *terms = reset ? c->rotsum_terms.exchange(0) : c->rotsum_terms.load();
-    return MHE_OK;
+    return groupsum_stats(c, &mhe_ctx::rotsum_sums, &mhe_ctx::rotsum_terms, sums, terms, reset);
 }
 
 MHE_EXPORT int mhe_rotate_sum(mhe_ctx *c, int count, const uint64_t *const *in, const uint32_t *elts,
@@ -593,10 +511,7 @@ MHE_EXPORT int mhe_rotate_sum(mhe_ctx *c, int count, const uint64_t *const *in, 
     hipStream_t st = S(s);
     const int L = limbs;
     const size_t n = c->n, ps = (size_t)L << c->log_n;
-    // group[] non-decreasing from 0 to groups - 1 without a gap: no group is empty
-    for (int i = 0, prev = 0; i < count; prev = group[i++])
-        if (group[i] != prev && !(i > 0 && group[i] == prev + 1)) return fail(MHE_ERR_ARG, "invalid argument");
-    if ((count ? group[count - 1] + 1 : 0) != groups) return fail(MHE_ERR_ARG, "invalid argument");
+    if (!check_groups(group, count, groups)) return fail(MHE_ERR_ARG, "invalid argument");
     for (int g = 0; g < groups; g++)
         if (!out[g]) return fail(MHE_ERR_ARG, "Galois key not present");
     // every key is checked before the first launch, so a bad key leaves no output half-written
@@ -629,93 +544,53 @@ MHE_EXPORT int mhe_rotate_sum(mhe_ctx *c, int count, const uint64_t *const *in, 
     }
     // all scratch before the first launch: a failed growth leaves every output as it was
     Workspace *w;
-    if ((r = get_rotsum(c, st, std::min(count, MHE_MAXB), L, &w))) return r;
-    const size_t rs_per = (4 * (size_t)w->rs_limbs + 2) * n;
-    auto A_of = [&](int slot) { return w->rs_base.p + (size_t)slot * rs_per; };
-    auto T_of = [&](int slot) { return A_of(slot) + 2 * (size_t)(L + 1) * n; };
+    if ((r = get_groupsum(c, st, std::min(count, MHE_MAXB), L, &Workspace::rotsum, &w))) return r;
+    const SumPool &sp = w->rotsum;
     // rounds of at most MHE_MAXB groups: their entries, those of one key side by side (a launch of
     // them shares the key stream, k_ks_row_mac share), in chunks of at most MHE_MAXB that cut across
     // groups, then one ModDown forward NTT per limb for all of the round's groups
-    std::vector<int> order(count);
-    for (int i = 0; i < count; i++) order[i] = i;
-    int i0 = 0;
-    for (int g0 = 0; g0 < groups; g0 += MHE_MAXB)
+    for (const GroupSumRound &round : plan_group_sums(count, group, groups, MHE_MAXB, keys))
     {
-        const int G = std::min(MHE_MAXB, groups - g0);
-        int i1 = i0;
-        while (i1 < count && group[i1] < g0 + G) i1++;
-        std::stable_sort(order.begin() + i0, order.begin() + i1, [&](int a, int b) { return keys[a] < keys[b]; });
-        bool started[MHE_MAXB] = {}; // the round's groups that a chunk has written
-        for (int b0 = i0; b0 < i1; b0 += MHE_MAXB)
+        for (const GroupSumChunk &ch : round.chunks)
         {
-            const int B = std::min(MHE_MAXB, i1 - b0);
             // permuted (c0, c1) of every entry into its scratch, then the key switch of the permuted c1
             // up to the key products (evaluator.cpp:2193-2214, 2281-2463)
             GalPtrs gp{};
             KsJob jobs[MHE_MAXB];
-            RotSumPtrs rp{};
-            int Z = 0, zslot[MHE_MAXB];
-            rp.B = B;
-            for (int e = 0; e < B; e++)
+            GroupSumPtrs rp = groupsum_ptrs(ch, w, sp, 1, L, n);
+            for (int e = 0; e < rp.B; e++)
             {
-                const int i = order[b0 + e];
+                const int i = ch.entries[e];
                 gp.in[e] = in[i];
                 gp.out[e] = w->e[e].ct3;
                 gp.elt[e] = elts[i];
                 jobs[e] = KsJob{ nullptr, w->e[e].ct3 + ps, keys[i], key_limbs[i], nullptr };
-                rp.acc[e] = w->e[e].acc;
-                rp.perm[e] = w->e[e].ct3;
-                const int slot = group[i] - g0;
-                int z = 0;
-                while (z < Z && zslot[z] != slot) z++;
-                if (z == Z)
-                {
-                    zslot[Z++] = slot;
-                    rp.A[z] = A_of(slot);
-                    rp.T[z] = T_of(slot);
-                    rp.out[z] = out[group[i]];
-                    rp.first[z] = started[slot] ? 0 : 1; // the group's first chunk
-                    rp.write0[z] = (!started[slot] && !accumulate) ? 1 : 0;
-                    started[slot] = true;
-                }
-                rp.zof[e] = z;
+                rp.x[e] = w->e[e].ct3;
             }
-            if ((r = permute_batch(c, gp, B, L, st, true))) return r;
-            int special_inv_done = 0;
-            if ((r = run_switch_key_batch(c, jobs, B, L, st, 0, &special_inv_done))) return r;
-            // each entry's special limbs through their own inverse NTT, [0, 2P)
-            JobB<JobStrided> sj;
-            sj.per = 2;
-            for (int e = 0; e < B; e++) sj.j[e] = special_limbs(c, w->e[e].acc, L);
-            if (!special_inv_done) inv_row(sj, c->log_n, 2 * B, c->nm, st);
-            inv_col(sj, c->log_n, 2 * B, c->nm, st);
-            hipLaunchKernelGGL(k_rotsum_acc, dim3((unsigned)(n / 512), (unsigned)(2 * L), (unsigned)Z), dim3(256), 0, st,
-                               rp, c->primes, L, c->K, c->log_n);
-            HIP_LAUNCH_CHECK();
+            for (int z = 0; z < ch.Z(); z++)
+            {
+                rp.X[z] = out[round.g0 + ch.slot[z]];
+                rp.firstx[z] = (ch.first[z] && !accumulate) ? 1 : 0; // out[0] written, not added to
+            }
+            if ((r = permute_batch(c, gp, rp.B, L, st, true))) return r;
+            if ((r = groupsum_fold(c, w, jobs, rp, ch.Z(), L, st))) return r;
         }
         // the round's groups: T -> NTT(T) in place, then out += (A - NTT(T)) P^-1 (out[1] written
         // when not accumulating)
-        JobB<JobFwdPlain> fc;
-        fc.per = 2 * L;
-        JobB<JobModDownRow> dr;
-        dr.per = 2 * L;
-        for (int z = 0; z < G; z++)
+        JobB<JobFwdPlain> fc(2 * L);
+        JobB<JobModDownRow> dr(2 * L);
+        for (int z = 0; z < round.G; z++)
         {
-            fc.j[z] = fwd_plain(c, T_of(z), T_of(z), L, 0);
-            dr.j[z] = JobModDownRow{ T_of(z), A_of(z), out[g0 + z], c->primes, c->tw, c->invq, L, c->K, c->log_n };
+            u64 *T = sp.at(z, 1, L, n);
+            fc.j[z] = fwd_plain(c, T, T, L, 0);
+            dr.j[z] = JobModDownRow{ T, sp.at(z, 0, L, n), out[round.g0 + z], c->primes, c->tw, c->invq, L, c->K, c->log_n };
             dr.j[z].fp = c->nm.fp ? 1 : 0;
             dr.j[z].c1_write = accumulate ? 0 : 1;
         }
-        fwd_col(fc, c->log_n, 2 * L * G, c->nm, st);
-        fwd_row(dr, c->log_n, 2 * L * G, c->nm, st);
+        fwd_col(fc, c->log_n, 2 * L * round.G, c->nm, st);
+        fwd_row(dr, c->log_n, 2 * L * round.G, c->nm, st);
         HIP_LAUNCH_CHECK();
-        for (int z = 0; z < G; z++)
-        {
-            int terms = 0;
-            for (int i = i0; i < i1; i++) terms += group[i] == g0 + z;
-            count_op(c, MHE_OPK_ADDSUB, L, 2ull * (unsigned long long)(terms - 1 + (accumulate ? 1 : 0)));
-        }
-        i0 = i1;
+        groupsum_count_adds(c, round, L, accumulate ? 1 : 0, nullptr);
     }
     c->rotsum_sums += (unsigned long long)groups;
     c->rotsum_terms += (unsigned long long)count;
