@@ -117,6 +117,17 @@ static KsPtrs ks_ptrs(Workspace *w, const KsJob *jobs, int B, u64 *const *accs, 
     return kp;
 }
 
+// The digit-major ModUp column pass (k_modup_col) of B entries at L limbs, every output prime, in the
+// output-prime groups that modup_groups picks for the launch's size (MHE_KS_COLGROUPS=n forces n).
+// Counted for mhe_modup_stats.
+static void ks_modup_col(mhe_ctx *c, const KsPtrs &kp, int B, int L, int pack, hipStream_t st)
+{
+    const int IG = modup_groups(c->ks_colgroups, c->log_n, L, B, L + 1);
+    modup_col(kp, B, c->primes, c->tw, L, c->K, c->log_n, c->nm_ks, 0, L + 1, IG, pack, st);
+    c->modup_launches++;
+    c->modup_ig_sum += (unsigned long long)IG;
+}
+
 // One key for every entry of a launch of several: XCD-grouped entries (k_ks_row_mac share).
 static int ks_shared_key(const mhe_ctx *c, const KsJob *jobs, int B)
 {
@@ -294,11 +305,11 @@ static int run_switch_key_batch(mhe_ctx *c, const KsJob *jobs, int B, int L, hip
         //      sized for the Infinity Cache measured slower at every size).
         // 48-bit intermediate (ntt.h tile16): only k_modup_col writes it, so only with column groups
         // and it leaves the FP sweeps' other limbs as doubles (MHE_INTER_F64), as the fused MAC reads them
-        const int pack = c->ks_colgroups > 0 ? ((c->ks_pack ? 1 : 0) | MHE_INTER_F64) : 0;
+        const int pack = c->ks_colgroups != 0 ? ((c->ks_pack ? 1 : 0) | MHE_INTER_F64) : 0;
         const KsPtrs kp = ks_ptrs(w, jobs, B, nullptr, nullptr);
         hipEvent_t *tc = timing_slot(c, w, TK_MODUP_COL, st);
-        if (c->ks_colgroups > 0)
-            modup_col(kp, B, c->primes, c->tw, L, c->K, log_n, c->nm_ks, 0, L + 1, std::min(c->ks_colgroups, L + 1), pack, st);
+        if (c->ks_colgroups != 0)
+            ks_modup_col(c, kp, B, L, pack, st);
         else
         {
             JobB<JobModUpCol> j((L + 1) * L);

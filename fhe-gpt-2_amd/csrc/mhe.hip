@@ -295,7 +295,11 @@ struct mhe_ctx
     // shared-key launches at n = 2^16 (FP64): two entries per workgroup (k_ks_row_mac NE = 2; MHE_KS_PAIR=0: one)
     int ks_pair = 1;
     std::atomic<unsigned long long> ks_paired{ 0 }, ks_single{ 0 }; // mhe_ks_pair_stats
-    int ks_colgroups = 9; // ModUp column pass: output-prime groups per digit (MHE_KS_COLGROUPS; 0 = one job per (I, J))
+    // ModUp column pass: output-prime groups per digit.  -1: by the launch's size (ntt.h modup_groups);
+    // MHE_KS_COLGROUPS=n: n groups; 0: one job per (I, J) (the generic column pass)
+    int ks_colgroups = -1;
+    // k_modup_col launches and the sum of their group counts IG (mhe_modup_stats)
+    std::atomic<unsigned long long> modup_launches{ 0 }, modup_ig_sum{ 0 };
     int ks_pack = 1; // n = 2^16: ModUp intermediate of primes < 2^48 stored in 48 bits (MHE_KS_PACK=0: 64 bits)
     int icol_fused = 1; // ModDown / rescale: inverse column pass fused into the lift column pass (MHE_ICOL_FUSED=0: separate)
     int galois_fused = 1; // apply_galois: one permutation launch, c1 written by the ModDown (MHE_GALOIS_FUSED=0: SEAL's order with a zero fill)
@@ -849,7 +853,7 @@ MHE_EXPORT int mhe_ctx_create(mhe_ctx **out, int log_n, const uint64_t *moduli, 
     if (const char *f = getenv("MHE_HMULT_FUSED")) c->hmult_fused = atoi(f);
     if (const char *f = getenv("MHE_KS_SHARE")) c->ks_share = atoi(f);
     if (const char *f = getenv("MHE_KS_PAIR")) c->ks_pair = atoi(f);
-    if (const char *f = getenv("MHE_KS_COLGROUPS")) c->ks_colgroups = atoi(f);
+    if (const char *f = getenv("MHE_KS_COLGROUPS")) c->ks_colgroups = std::max(0, atoi(f));
     if (const char *f = getenv("MHE_KS_PACK")) c->ks_pack = atoi(f);
     if (const char *f = getenv("MHE_GALOIS_FUSED")) c->galois_fused = atoi(f);
     if (const char *f = getenv("MHE_ICOL_FUSED")) c->icol_fused = atoi(f);

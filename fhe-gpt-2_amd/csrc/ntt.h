@@ -251,6 +251,11 @@ struct NttArithF
         : q((double)p.q), qinv(1.0 / (double)p.q), tw(reinterpret_cast<const TwF *>(reinterpret_cast<const char *>(t) + delta))
     {
     }
+    // with q and 1/q already as doubles (PrimeDev::qd, qi: the same two values, made on the host)
+    __device__ NttArithF(const PrimeDev &, const Tw *t, long long delta, double qd, double qi)
+        : q(qd), qinv(qi), tw(reinterpret_cast<const TwF *>(reinterpret_cast<const char *>(t) + delta))
+    {
+    }
     __device__ T in(u64 x) const { return (double)x; }
     __device__ T in52(u64 x) const { return fp_from_u52(x); } // x < 2^52: a canonical residue
     __device__ u64 out(T x) const { return fp_canon(x, q, qinv); }
@@ -1102,7 +1107,8 @@ struct KsPtrs
 };
 
 constexpr int MHE_MODUP_OCC = 3; // waves per SIMD the ModUp column pass is compiled for (168 VGPRs)
-constexpr int MHE_MODUP_TWG = 5; // output primes per group whose twiddles the ModUp column pass stages in LDS
+constexpr int MHE_MODUP_TWG = 5; // output primes whose twiddles the ModUp column pass holds in LDS at a time (a ring)
+constexpr int MHE_MODUP_GMAX = 64; // output primes per workgroup at most: the kernel keeps its group as 64-bit masks
 // MIX (with FP): output primes >= 2^51 (the GPT-2 chain's special prime) take the integer sweep.
 // The integer and MIX variants get 2 waves/SIMD: at 3 (168 VGPRs) they spilled 116-124 bytes per
 // lane, and each scratch reload waits for every store in flight (one vmcnt for loads and stores)
@@ -1134,7 +1140,7 @@ __global__ __launch_bounds__(256, (FP && !MIX) ? MHE_MODUP_OCC : MHE_MODUP_OCC_I
     constexpr bool PG = LOGR == 8 && TPS == 16;
     __shared__ T lds[S * LD];
     // The column-pass twiddles of the group's output primes (entries 1 .. R-1 of each prime's table,
-    // the same for every column), staged once per workgroup.  Read from global memory stage by stage
+    // the same for every column), MHE_MODUP_TWG primes at a time (a ring, below).  Read from global memory stage by stage
     // instead, each twiddle load's s_waitcnt also waited for the previous prime's stores (one
     // counter for loads and stores), so compute and stores of consecutive primes never overlapped.
     __shared__ Tw twc[MHE_MODUP_TWG * R];
@@ -1168,23 +1174,67 @@ __global__ __launch_bounds__(256, (FP && !MIX) ? MHE_MODUP_OCC : MHE_MODUP_OCC_I
 #pragma unroll
     for (int e = 0; e < E; e++) x[e] = src[c + ((u32)(t + TPS * e) << logC)];
     const u64 qJ = primes[J].q;
-    // twiddles of the group's primes into LDS (16 B each: the FP table (w, w/q) or the integer one
-    // (w, Shoup), whichever the prime's sweep uses); groups wider than MHE_MODUP_TWG read global
-    const bool twl_on = i_hi - i_lo <= MHE_MODUP_TWG; // uniform per workgroup
-    if (twl_on)
+    // The group's output primes by sweep, as bit masks over I - i_lo (at most 64 primes per group:
+    // modup_groups): lane l of every wave classifies prime i_lo + l, so the ballots are the same in all
+    // four waves and uniform.  I == J is in no mask.
+    u64 mk_lazy, mk_full, mk_int;
     {
-        const int ng = i_hi - i_lo;
-        for (int k = tid; k < ng * R; k += 256)
-        {
-            const int g = k / R, idx = k % R;
-            const int I = i_lo + g;
-            const int pi = (I == L) ? K - 1 : I;
-            const bool fpt = FP && primes[pi].q < (1ull << 51);
-            const char *base = reinterpret_cast<const char *>(tw_all + ((size_t)pi << log_n)) + (fpt ? twd : 0);
-            twc[k] = reinterpret_cast<const Tw *>(base)[idx];
-        }
-        lds_barrier(); // twiddles visible
+        const int I = i_lo + (tid & 63);
+        const bool in = I < i_hi && I != J;
+        const int Ic = min(I, i_hi - 1); // a group is never empty (modup_groups): a prime to read in every lane
+        const u64 q = primes[(Ic == L) ? K - 1 : Ic].q;
+        const bool lz = FP && q < (1ull << 47), fl = FP && !lz && q < (1ull << 51);
+        mk_lazy = __ballot(in && lz);
+        mk_full = __ballot(in && fl);
+        mk_int = (!FP || MIX) ? __ballot(in && !lz && !fl) : 0;
     }
+    // twc is a ring of MHE_MODUP_TWG one-prime slots (16 B per twiddle: the FP table (w, w/q) or the
+    // integer one (w, Shoup), whichever the prime's sweep uses), taken in the order the workgroup
+    // processes its primes: the lazy sweep, the non-lazy sweep, the integer sweep.  The k-th prime of
+    // that order lives in slot k % MHE_MODUP_TWG.  The first four are staged here; behind its
+    // transpose barrier every prime k puts prime k + 4 into the slot in front of its own (below), which
+    // is prime k - 1's, or the one slot left empty here.  So a group may hold any number of primes.
+    u64 ahead = mk_lazy; // what is left of the sweep `asweep` (0 lazy, 1 non-lazy, 2 integer)
+    int asweep = 0;
+    auto next_ahead = [&]() -> int { // the next prime to stage, -1 when none is left (uniform)
+        if (!ahead && asweep == 0)
+        {
+            ahead = mk_full;
+            asweep = 1;
+        }
+        if (!ahead && asweep == 1)
+        {
+            ahead = mk_int;
+            asweep = 2;
+        }
+        if (!ahead) return -1;
+        const int b = __builtin_ctzll(ahead);
+        ahead &= ahead - 1;
+        return i_lo + b;
+    };
+    auto tw_src = [&](int I) -> const Tw * {
+        const int pi = (I == L) ? K - 1 : I;
+        const bool fpt = ((mk_lazy | mk_full) >> (I - i_lo)) & 1;
+        return reinterpret_cast<const Tw *>(reinterpret_cast<const char *>(tw_all + ((size_t)pi << log_n)) + (fpt ? twd : 0));
+    };
+    {
+        // every load first, then the writes (a slot the order does not reach reads the group's first
+        // prime and writes nothing)
+        static_assert(MHE_MODUP_TWG == 5, "the staging below is written out for five slots");
+        // (nothing behind a branch, or the compiler waits for these loads again inside the loop, with
+        // the stores: a slot the order does not reach gets the group's first prime, and with R < 256
+        // lanes R and up repeat the writes of lanes 0 .. R-1)
+        auto ld = [&](int I) { return tw_src(I >= 0 ? I : i_lo)[tid & (R - 1)]; };
+        auto st = [&](int k, const Tw &w) { twc[k * R + (tid & (R - 1))] = w; };
+        const int I0s = next_ahead(), I1s = next_ahead(), I2s = next_ahead(), I3s = next_ahead();
+        const Tw w0 = ld(I0s), w1 = ld(I1s), w2 = ld(I2s), w3 = ld(I3s);
+        st(0, w0);
+        st(1, w1);
+        st(2, w2);
+        st(3, w3);
+    }
+    lds_barrier(); // twiddles visible
+    int rp = 0; // ring slot of the next output prime, carried across the sweeps
     // FP: the digit residues (< 2^51, exact in a double) are converted once, not once per output
     // prime (u64 -> f64 is several VALU instructions)
     double xd[E];
@@ -1203,17 +1253,19 @@ __global__ __launch_bounds__(256, (FP && !MIX) ? MHE_MODUP_OCC : MHE_MODUP_OCC_I
         using AA = std::conditional_t<M == 0, NttArith<false>, std::conditional_t<M == 1, NttArithF<true>, NttArithF<false>>>;
         using VT = typename AA::T;
         VT *const lds_v = reinterpret_cast<VT *>(lds); // same 8-byte elements either way
-        for (int I = i_lo; I < i_hi; I++)
+        for (u64 todo = M == 1 ? mk_lazy : M == 2 ? mk_full : mk_int; todo; todo &= todo - 1)
         {
-            if (I == J) continue; // uniform per workgroup
+            const int I = i_lo + __builtin_ctzll(todo); // uniform per workgroup
             const int pi = (I == L) ? K - 1 : I;
             const PrimeDev p = primes[pi];
-            if (M == 1 && !(p.q < (1ull << 47))) continue;
-            if (M == 2 && (p.q < (1ull << 47) || !(p.q < (1ull << 51)))) continue;
-            if (M == 0 && FP && p.q < (1ull << 51)) continue; // mixed: the FP sweeps took it
-            const AA ar(p, tw_all + ((size_t)pi << log_n), twd);
+            // FP: q and 1/q as doubles from the prime's table entry (the host makes them with the
+            // expressions NttArithF's constructor uses, both correctly rounded: the same doubles)
+            const AA ar = [&] {
+                if constexpr (M != 0) return AA(p, tw_all + ((size_t)pi << log_n), twd, p.qd, p.qi);
+                else return AA(p, tw_all + ((size_t)pi << log_n), twd);
+            }();
             using TWA = typename AA::TW;
-            const TWA *tl = reinterpret_cast<const TWA *>(&twc[(I - i_lo) * R]);
+            const TWA *tl = reinterpret_cast<const TWA *>(&twc[rp * R]);
             VT v[E];
             // FP, uniform per workgroup: a lazy prime whose packed exit is folded into the last stage
             // (below), and a non-packed limb left as doubles for the fused MAC
@@ -1240,17 +1292,11 @@ __global__ __launch_bounds__(256, (FP && !MIX) ? MHE_MODUP_OCC : MHE_MODUP_OCC_I
                 // setup
                 fwd_first_phase_s<E, LOGE>(ar, v, xd, red, reinterpret_cast<const char *>(tw_all + ((size_t)pi << log_n)) + twd);
             }
-            else if (twl_on)
-            {
-#pragma unroll
-                for (int s = 0; s < LOGE; s++)
-                    ar.template fwd_tab<E>(v, 1 << (LOGE - 1 - s), tl, [&](int e) { return (1 << s) + (e >> (LOGE - s)); });
-            }
             else
             {
 #pragma unroll
                 for (int s = 0; s < LOGE; s++)
-                    ar.template fwd<E>(v, 1 << (LOGE - 1 - s), [&](int e) { return (1 << s) + (e >> (LOGE - s)); });
+                    ar.template fwd_tab<E>(v, 1 << (LOGE - 1 - s), tl, [&](int e) { return (1 << s) + (e >> (LOGE - s)); });
             }
             if constexpr (PG)
             {
@@ -1287,35 +1333,30 @@ __global__ __launch_bounds__(256, (FP && !MIX) ? MHE_MODUP_OCC : MHE_MODUP_OCC_I
             // a lazy prime's last stage is taken apart from the others: with `fold` it reduces x as the
             // non-lazy butterfly does, so |x'|, |y'| <= 2q + 1 < 2^47 (q < 2^46) fit the packed slot
             // with no reduction of their own
+            // The ring's refill.  Every wave is past the transpose barrier above, so every wave has
+            // finished the previous output prime's second phase, the only reader of that prime's slot:
+            // the slot is free.  Each lane loads one twiddle of the prime four places on in the order and
+            // writes it after this prime's second phase, in front of the next barrier.  With
+            // nothing left to stage the lanes copy this prime's twiddles instead: no prime to come reads
+            // that slot, and neither the load nor the write sits behind a branch (as above).
+            const int rq = rp == 0 ? MHE_MODUP_TWG - 1 : rp - 1; // the slot in front of this prime's
+            const int In = next_ahead();                         // uniform
+            const Tw refill = tw_src(In >= 0 ? In : I)[tid & (R - 1)];
             constexpr int S_END = M == 1 ? LOGR - 1 : LOGR;
-            if (twl_on)
-            {
 #pragma unroll
-                for (int s = LOGE; s < S_END; s++)
-                    ar.template fwd_tab<E>(v, 1 << (LOGR - 1 - s), tl,
-                                           [&](int e) { return (1 << s) + ((E * t + e) >> (LOGR - s)); });
-            }
-            else
-            {
-#pragma unroll
-                for (int s = LOGE; s < S_END; s++)
-                    ar.template fwd<E>(v, 1 << (LOGR - 1 - s),
+            for (int s = LOGE; s < S_END; s++)
+                ar.template fwd_tab<E>(v, 1 << (LOGR - 1 - s), tl,
                                        [&](int e) { return (1 << s) + ((E * t + e) >> (LOGR - s)); });
-            }
             if constexpr (M == 1)
             {
                 auto ix = [&](int e) { return (1 << (LOGR - 1)) + ((E * t + e) >> 1); };
-                if (fold)
-                {
-                    if (twl_on) ar.template fwd_tab_full<E>(v, 1, tl, ix);
-                    else ar.template fwd_full<E>(v, 1, ix);
-                }
-                else
-                {
-                    if (twl_on) ar.template fwd_tab<E>(v, 1, tl, ix);
-                    else ar.template fwd<E>(v, 1, ix);
-                }
+                if (fold) ar.template fwd_tab_full<E>(v, 1, tl, ix);
+                else ar.template fwd_tab<E>(v, 1, tl, ix);
             }
+            // (in front of this prime's stores: the compiler waits for a vector load with vmcnt(0)
+            // whenever stores are in flight too, so behind them the write would drain them; here it
+            // waits for the previous prime's, a second phase old)
+            twc[rq * R + (tid & (R - 1))] = refill;
             u64 *dst = modup + (((size_t)(I - I0) * L + J) << log_n);
             if (packed) // uniform per workgroup
             {
@@ -1387,6 +1428,7 @@ __global__ __launch_bounds__(256, (FP && !MIX) ? MHE_MODUP_OCC : MHE_MODUP_OCC_I
                     for (int e = 0; e < E; e++) st_nt<0>(d0 + (size_t)e * stride, ar.out(v[e]));
                 }
             }
+            rp = rp == MHE_MODUP_TWG - 1 ? 0 : rp + 1;
             if constexpr (!PG) lds_barrier(); // lds is rewritten by the next output prime (its stores need not land)
         }
     };
@@ -1398,6 +1440,22 @@ __global__ __launch_bounds__(256, (FP && !MIX) ? MHE_MODUP_OCC : MHE_MODUP_OCC_I
     }
     else
         sweep(std::integral_constant<int, 0>{});
+}
+
+// Output-prime groups per digit (k_modup_col's IG) for a launch of B entries at L limbs and Icnt output
+// primes.  forced > 0 (MHE_KS_COLGROUPS=n): n groups.  Otherwise by the launch's size: a workgroup's
+// fixed cost (the digit's loads and conversions, the first twiddles, a barrier) is paid once per group,
+// so a launch takes the fewest groups that still give it MHE_MODUP_FILL workgroups, and never more than
+// MHE_MODUP_IGMAX.  Either way within 1 .. Icnt and with at most MHE_MODUP_GMAX primes per group.
+constexpr int MHE_MODUP_FILL = 3600; // workgroups (768 are resident on 256 CUs): profiles/modup_stream
+constexpr int MHE_MODUP_IGMAX = 9;
+static inline int modup_groups(int forced, int log_n, int L, int B, int Icnt)
+{
+    const int LOGR = (log_n + 1) / 2, LOGT = LOGR <= 7 ? 3 : 4;
+    const long long W = (long long)(1 << (log_n - LOGR)) / (256 >> LOGT) * L * B; // workgroups per group
+    int IG = forced > 0 ? forced : (int)std::min<long long>(MHE_MODUP_IGMAX, (MHE_MODUP_FILL + W - 1) / std::max<long long>(W, 1));
+    IG = std::max(IG, (Icnt + MHE_MODUP_GMAX - 1) / MHE_MODUP_GMAX);
+    return std::max(1, std::min(IG, Icnt));
 }
 
 template <int LOGR, bool FP, bool MIX = false>

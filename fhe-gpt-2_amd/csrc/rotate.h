@@ -97,7 +97,7 @@ template <class F> static void with_rotation_count(int R, F f)
 
 static bool hoist_ok(const mhe_ctx *c)
 {
-    return c->ks_hoist && c->ks_fused && c->galois_fused && c->ks_colgroups > 0 && c->nm.fp == 1 && c->nm_ks.fp == 1 &&
+    return c->ks_hoist && c->ks_fused && c->galois_fused && c->ks_colgroups != 0 && c->nm.fp == 1 && c->nm_ks.fp == 1 &&
            c->cmodf;
 }
 
@@ -193,7 +193,6 @@ static int run_galois_hoisted(mhe_ctx *c, const u64 *const *in, int H, int count
     if (r) return r;
     const int log_n = c->log_n;
     const size_t n = c->n, ps = (size_t)L * n;
-    const int IG = std::min(c->ks_colgroups, L + 1);
     std::vector<const u64 *> masks(count);
     std::vector<u32> elt_inv(count);
     for (int i = 0; i < count; i++)
@@ -219,7 +218,7 @@ static int run_galois_hoisted(mhe_ctx *c, const u64 *const *in, int H, int count
             kp.coeff[h] = w->e[h].coeff;
             kp.inter[h] = w->e[h].modup;
         }
-        modup_col(kp, H, c->primes, c->tw, L, c->K, log_n, c->nm_ks, 0, L + 1, IG, 0, st);
+        ks_modup_col(c, kp, H, L, 0, st);
         auto row = [&](auto brev) {
             JobB<JobModUpRowH<decltype(brev)::value>> rj((L + 1) * L);
             for (int h = 0; h < H; h++) rj.j[h] = { w->e[h].modup, w->hoist[h], c->primes, c->tw, L, c->K, log_n };
@@ -300,7 +299,7 @@ static int run_galois_hoisted(mhe_ctx *c, const u64 *const *in, int H, int count
     HIP_LAUNCH_CHECK();
     // 3. per MHE_MAXB rotations: c0 / c1 permuted into out, the classic ModUp + MAC of flagged
     //    inputs (their kernels return at once otherwise), the ModDown (c1 written)
-    const int pack = (c->ks_pack && c->ks_colgroups > 0) ? 1 : 0;
+    const int pack = (c->ks_pack && c->ks_colgroups != 0) ? 1 : 0;
     const int pack_col = pack | MHE_INTER_F64; // the column pass in front of the fused MAC (ntt.h)
     std::vector<int> order(count);
     for (int i = 0; i < count; i++) order[i] = i;
@@ -331,7 +330,7 @@ static int run_galois_hoisted(mhe_ctx *c, const u64 *const *in, int H, int count
         count_op(c, MHE_OPK_KEYSWITCH, L, (unsigned long long)B);
         intt_targets(c, w, c1, B, L, flagged, st);
         const KsPtrs kp = ks_ptrs(w, jobs, B, accs, flagged);
-        modup_col(kp, B, c->primes, c->tw, L, c->K, log_n, c->nm_ks, 0, L + 1, IG, pack_col, st);
+        ks_modup_col(c, kp, B, L, pack_col, st);
         ks_row_mac_chunk(kp, B, c->primes, c->tw, L, c->K, log_n, c->nm_ks, 0, L + 1, pack, kpack, ks_shared_key(c, jobs, B),
                          ks_pair_of(c), c->itw, 0, st);
         HIP_LAUNCH_CHECK();
@@ -487,6 +486,18 @@ MHE_EXPORT int mhe_ks_pair_stats(mhe_ctx *c, uint64_t *paired, uint64_t *single,
     if (!valid_ctx(c) || !paired || !single) return fail(MHE_ERR_ARG, "invalid argument");
     *paired = reset ? c->ks_paired.exchange(0) : c->ks_paired.load();
     *single = reset ? c->ks_single.exchange(0) : c->ks_single.load();
+    return MHE_OK;
+}
+
+// The digit-major ModUp column pass (k_modup_col; keyswitch.h ks_modup_col): launches counts its
+// launches since the last reset, whether by a key switch, an HMult or a rotation pipeline, and ig_sum
+// adds up their output-prime groups per digit (the kernel's IG): ig_sum == n * launches says that every
+// launch ran with n groups.  The generic column pass (MHE_KS_COLGROUPS=0) is not counted.
+MHE_EXPORT int mhe_modup_stats(mhe_ctx *c, uint64_t *launches, uint64_t *ig_sum, int reset)
+{
+    if (!valid_ctx(c) || !launches || !ig_sum) return fail(MHE_ERR_ARG, "invalid argument");
+    *launches = reset ? c->modup_launches.exchange(0) : c->modup_launches.load();
+    *ig_sum = reset ? c->modup_ig_sum.exchange(0) : c->modup_ig_sum.load();
     return MHE_OK;
 }
 

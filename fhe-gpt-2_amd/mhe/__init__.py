@@ -38,6 +38,7 @@ SIGNATURES = {
     "mhe_hoist_stats": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
                                        ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
     "mhe_ks_pair_stats": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
+    "mhe_modup_stats": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
     "mhe_debug_fail_alloc": (ctypes.c_int, [vp, ctypes.c_int]),
     "mhe_debug_fail_switch": (ctypes.c_int, [vp, ctypes.c_int]),
     "mhe_alloc_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
@@ -270,6 +271,12 @@ class Engine:
         p, s = ctypes.c_uint64(), ctypes.c_uint64()
         _check(lib().mhe_ks_pair_stats(self._h, ctypes.byref(p), ctypes.byref(s), 1 if reset else 0))
         return p.value, s.value
+
+    def modup_stats(self, reset=False):
+        """(ModUp column-pass launches, the sum of their output-prime groups per digit)."""
+        n, g = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().mhe_modup_stats(self._h, ctypes.byref(n), ctypes.byref(g), 1 if reset else 0))
+        return n.value, g.value
 
     @staticmethod
     def alloc_stats(reset=False):

@@ -147,6 +147,11 @@ int mhe_hoist_stats(mhe_ctx *ctx, uint64_t *rotations, uint64_t *mac_launches, u
  * at context creation turns pairing off) and those that ran one.  A batch of an odd number of entries
  * counts once in each. */
 int mhe_ks_pair_stats(mhe_ctx *ctx, uint64_t *paired, uint64_t *single, int reset);
+/* Launches of the digit-major ModUp column pass (of key switches, HMults and rotation pipelines) since
+ * the last reset, and the sum over them of the output-prime groups per digit each ran with: by the
+ * launch's size, or MHE_KS_COLGROUPS=n at context creation for n groups (at most one per output
+ * prime).  ig_sum == n * launches: every launch ran with n groups. */
+int mhe_modup_stats(mhe_ctx *ctx, uint64_t *launches, uint64_t *ig_sum, int reset);
 /* Device scratch the context holds: per-stream workspaces (key-switch / rescale scratch for up to
  * 8 batch entries at the key level, and the group accumulators of mhe_rotate_sum on the streams
  * that called it), hoisting buffers, Galois negation-mask tables, and the number of streams with a
