@@ -35,6 +35,35 @@
 //   non-lazy (q < 2^51): x enters as it stands when q_J <= 2q, so |x|, |y| < 2q.  The first
 //     stage reduces x itself (|x| <= 2^53) and takes |y| <= 2q into fp_mulmod, the bound B of
 //     the paragraph above; from there on |.| <= 2q + 1 as for reduced input.
+//
+// Scheduled reduction of x (ntt.h k_modup_col's non-lazy sweep and k_ks_row_mac's non-lazy row
+// stages; tests/fp_sched.cpp checks each figure on the host).  A non-lazy prime (q < 2^51) need not
+// reduce x in every stage: a value that is x in one stage and y in the next is reduced by the
+// product, and fp_mulmod stays exact well beyond |y| = 2q + 1 (its comment).  Write R for a stage
+// that reduces x (fwd_bfly_f) and L for one that does not (the arithmetic of fwd_bfly_f_lazy).  With
+// e(b) = 3 b 2^-54 + 1/2, the quotient error of fp_mulmod for |y| <= b, a stage maps a bound b on
+// |x|, |y| to
+//     R: q/2 + 2 + e(b) q   (the centred reduction of |x| <= 2^53 is within q/2 + 2)
+//     L: b + e(b) q
+// and fp_sched_reduce (below) makes the stages alternate, L first in the row pass and R last in the
+// column pass, so no two L stages follow each other, not across the two passes either.  For q < 2^51:
+//   fixed point: b_R = 2.4517q after an R stage, b_L = 3.8710q after an L stage.  Any entry within
+//     b_R keeps every later value within these two, for any number of stages and chained passes:
+//     every sum is an exact integer below 3.88q < 2^53, every y that enters fp_mulmod is within
+//     3.88q (e <= 1.955, |h - kq| + ulp(h)/2 <= 1.955q + 2^51 < 2^53: the fma is exact), and every x
+//     that is reduced is within 2^53.  An L stage needs its inputs within b_R; an R stage takes b_L.
+//   column pass of 8 or 6 stages, L R L R ...: from an unreduced lift (|x|, |y| < 2q, or the 2q + 1
+//     of the paragraph above) the bounds are 3.25q, 2.22q, 3.56q, 2.34q, 3.71q, 2.39q, 3.79q, 2.42q;
+//     from a reduced lift (<= q/2 + 1) 1.19q, 1.45q, 2.49q, 1.94q, 3.16q, 2.19q, 3.51q, 2.32q.
+//   column pass of 7 stages, R L R L R L R: from either lift at most 1.75q, 2.91q, 2.09q, 3.38q,
+//     2.27q, 3.62q, 2.36q.
+//   The column pass leaves |w| <= 2.46q in a slot of doubles (its packed exit, fp_to_s48, reduces
+//     |x| <= 2^53 as before); the row pass enters with that, or with a canonical or centred residue,
+//     runs L R L R ... and ends within 2.46q (8 or 6 stages) or 3.88q (7 stages).  The fused MAC
+//     reduces the digit first (fp_reduce of |x| <= 2^53: within q/2 + 2 <= 2^51, fp_mulmod_gen's
+//     condition; its products stay within 1.25q).
+//   Primes below 2^50 and 2^48 sit lower: b_L = 2.18q and 1.63q.
+// Every output is canonicalised or reduced into its slot as before: the words that leave are the same.
 #pragma once
 #include <stdint.h>
 #ifdef MHE_FPARITH_HOST
@@ -97,7 +126,8 @@ __device__ __forceinline__ double fp_mulmod_gen(double a, double b, double q, do
     return __builtin_fma(-k, q, h) + l;
 }
 
-// centered reduction: x - rint(x/q)*q, |result| <= q/2 + 1 for |x| <= 2^52.
+// centered reduction: x - rint(x/q)*q, |result| <= q/2 + 1 for |x| <= 2^52 and <= q/2 + 2 for
+// |x| <= 2^53 (fl(x/q) errs by at most |x/q| 2^-52, which is |x| 2^-52 in the remainder).
 __device__ __forceinline__ double fp_reduce(double x, double q, double qinv)
 {
     return __builtin_fma(-fp_rint(x * qinv), q, x);
@@ -194,16 +224,27 @@ __device__ __forceinline__ void inv_bfly_last_f(double &x, double &y, double nin
     y = fp_mulmod(fp_reduce(d, q, qinv), lw, lws, q);
 }
 
+// The schedule of the non-lazy primes' x reduction ("Scheduled reduction of x" in the header): does
+// stage a reduce x?  a counts from the boundary between the two passes of a transform: stage s of a
+// column pass of NS stages is a = s - NS (-NS .. -1), stage s of the row pass is a = s.  Odd stages
+// reduce, so the column pass always ends on a reduction and the row pass starts without one.
+constexpr bool fp_sched_reduce(int a)
+{
+    return (a & 1) != 0;
+}
+
 // One forward stage over the E values of a lane (pairs (e, e+gap), gap bit clear); LAZY (only
-// for q < 2^47) drops the reduction of x.
-template <int E, bool LAZY, class TwOf>
+// for q < 2^47) drops the reduction of x.  REDX = false: a non-lazy prime's stage that the schedule
+// above leaves without the reduction of x -- the arithmetic of the lazy butterfly under the
+// schedule's bounds, not the lazy primes'.
+template <int E, bool LAZY, bool REDX = true, class TwOf>
 __device__ __forceinline__ void fwd_stage_f(double (&v)[E], int gap, TwOf tw_of, double q, double qinv)
 {
 #pragma unroll
     for (int e = 0; e < E; e++)
         if (!(e & gap))
         {
-            if (LAZY)
+            if constexpr (LAZY || !REDX)
                 fwd_bfly_f_lazy(v[e], v[e + gap], *tw_of(e), q);
             else
                 fwd_bfly_f(v[e], v[e + gap], *tw_of(e), q, qinv);
@@ -212,7 +253,7 @@ __device__ __forceinline__ void fwd_stage_f(double (&v)[E], int gap, TwOf tw_of,
 
 // fwd_stage_f over two value vectors that take the same twiddles (two batch entries of one tile,
 // ntt.h k_ks_row_mac NE = 2): each twiddle is read once, into a local, and applied to both.
-template <int E, bool LAZY, class TwOf>
+template <int E, bool LAZY, bool REDX = true, class TwOf>
 __device__ __forceinline__ void fwd_stage_f2(double (&v0)[E], double (&v1)[E], int gap, TwOf tw_of, double q, double qinv)
 {
 #pragma unroll
@@ -220,7 +261,7 @@ __device__ __forceinline__ void fwd_stage_f2(double (&v0)[E], double (&v1)[E], i
         if (!(e & gap))
         {
             const TwF w = *tw_of(e);
-            if (LAZY)
+            if constexpr (LAZY || !REDX)
             {
                 fwd_bfly_f_lazy(v0[e], v0[e + gap], w, q);
                 fwd_bfly_f_lazy(v1[e], v1[e + gap], w, q);

@@ -106,7 +106,7 @@ __device__ __forceinline__ u32 tile16h(u32 idx)
 }
 // `pack` of the ModUp column pass: bit 0 = limbs of primes below 2^48 in the 48-bit form above
 // (n = 2^16; the fused MAC must be told the same); bit 1 (MHE_INTER_F64) = the FP sweeps leave every
-// other limb as a double congruent to the residue, |v| <= 2q + 1, instead of the canonical u64.  The
+// other limb as a double congruent to the residue, |v| <= 2.46q, instead of the canonical u64.  The
 // fused MAC's FP path (k_ks_row_mac) takes exactly that from a non-packed slot, so every column pass in
 // front of it sets the bit (or, the generic one, JobModUpCol::f64); the hoisted rotations' row pass
 // (JobModUpRowH) reads canonical words and leaves it clear.
@@ -288,6 +288,19 @@ struct NttArithF
     {
         fwd_stage_f2<E, LAZY>(v0, v1, gap, [&](int e) { return &tab[ix(e)]; }, q, qinv);
     }
+    // fwd_tab / fwd_tab2 of a stage under the schedule of the x reduction (fparith.h
+    // fp_sched_reduce; REDX = what it says of this stage).  The two hot key-switch kernels only: the
+    // generic passes reduce in every stage.  A lazy prime reduces in none, whatever REDX.
+    template <int E, bool REDX, class Ix>
+    __device__ void fwd_tab_sched(T (&v)[E], int gap, const TW *tab, Ix ix) const
+    {
+        fwd_stage_f<E, LAZY, REDX>(v, gap, [&](int e) { return &tab[ix(e)]; }, q, qinv);
+    }
+    template <int E, bool REDX, class Ix>
+    __device__ void fwd_tab2_sched(T (&v0)[E], T (&v1)[E], int gap, const TW *tab, Ix ix) const
+    {
+        fwd_stage_f2<E, LAZY, REDX>(v0, v1, gap, [&](int e) { return &tab[ix(e)]; }, q, qinv);
+    }
     template <int E, class Ix>
     __device__ void inv(T (&v)[E], int gap, Ix ix) const
     {
@@ -312,6 +325,18 @@ struct NttArith<true> : NttArithF<false>
 {
     using NttArithF<false>::NttArithF;
 };
+
+// f(integral_constant<int, s>) for s = S0 .. S1 - 1: a stage loop whose index is a constant
+// expression in the body (the schedule of the x reduction is chosen per stage at compile time)
+template <int S0, int S1, class F>
+__device__ __forceinline__ void stage_for(F &&f)
+{
+    if constexpr (S0 < S1)
+    {
+        f(std::integral_constant<int, S0>{});
+        stage_for<S0 + 1, S1>(f);
+    }
+}
 
 // Per-launch arithmetic selection: fp = every prime of the context is < 2^51; the deltas are
 // the byte offsets from the integer to the FP forward / inverse twiddle tables.
@@ -827,7 +852,9 @@ __global__ __launch_bounds__(256) void k_inv_col(Job job, int log_n, long long t
 // leaves the values in v.  red (uniform): xd is first reduced modulo the output prime; without it
 // the first stage reads xd as it stands (the caller's rule: fparith.h, "Unreduced lifts").  The
 // first stage is written in both arms so that neither needs a copy of xd.
-template <int E, int LOGE, class AR>
+// The stages follow the schedule of the x reduction for a column pass of NS stages (fparith.h
+// fp_sched_reduce; a lazy prime's arithmetic ignores it).
+template <int E, int LOGE, int NS, class AR>
 __device__ __forceinline__ void fwd_first_phase_s(const AR &ar, typename AR::T (&v)[E], const double (&xd)[E], bool red,
                                                   const void *ftab)
 {
@@ -839,28 +866,30 @@ __device__ __forceinline__ void fwd_first_phase_s(const AR &ar, typename AR::T (
         w1[k].x = __longlong_as_double((long long)g[2 * k]);
         w1[k].y = __longlong_as_double((long long)g[2 * k + 1]);
     }
-    auto stage = [&](int s) {
-        ar.template fwd_tab<E>(v, 1 << (LOGE - 1 - s), w1, [&](int e) { return (1 << s) + (e >> (LOGE - s)); });
+    auto stage = [&](auto sc) {
+        constexpr int s = decltype(sc)::value;
+        ar.template fwd_tab_sched<E, fp_sched_reduce(s - NS)>(v, 1 << (LOGE - 1 - s), w1,
+                                                              [&](int e) { return (1 << s) + (e >> (LOGE - s)); });
     };
+    using S0 = std::integral_constant<int, 0>;
     if (red)
     {
 #pragma unroll
         for (int e = 0; e < E; e++) v[e] = fp_reduce(xd[e], ar.q, ar.qinv);
-        stage(0);
+        stage(S0{});
         asm volatile("; lift reduced");
     }
     else
     {
 #pragma unroll
         for (int e = 0; e < E; e++) v[e] = xd[e];
-        stage(0);
+        stage(S0{});
         // (the markers keep the two arms apart: with their common stage sunk below them, the values
         // joined through 16 register copies, made in both arms; the copies would show as v_mov_b64 in
         // front of the branch and in DESIGN.md §18's per-prime instruction counts)
         asm volatile("; lift as it stands");
     }
-#pragma unroll
-    for (int s = 1; s < LOGE; s++) stage(s);
+    stage_for<1, LOGE>(stage);
 }
 
 // q < 2^47 (the lazy forward butterflies) as a scalar compare of the high word: the compiler folds any
@@ -1290,7 +1319,7 @@ __global__ __launch_bounds__(256, (FP && !MIX) ? MHE_MODUP_OCC : MHE_MODUP_OCC_I
                 const bool red = (int)(((M == 1 ? 4 : 2) * p.q - qJ) >> 32) < 0; // uniform
                 // the first phase's twiddles as scalar loads (fwd_first_phase_s), issued with the prime's
                 // setup
-                fwd_first_phase_s<E, LOGE>(ar, v, xd, red, reinterpret_cast<const char *>(tw_all + ((size_t)pi << log_n)) + twd);
+                fwd_first_phase_s<E, LOGE, LOGR>(ar, v, xd, red, reinterpret_cast<const char *>(tw_all + ((size_t)pi << log_n)) + twd);
             }
             else
             {
@@ -1343,10 +1372,23 @@ __global__ __launch_bounds__(256, (FP && !MIX) ? MHE_MODUP_OCC : MHE_MODUP_OCC_I
             const int In = next_ahead();                         // uniform
             const Tw refill = tw_src(In >= 0 ? In : I)[tid & (R - 1)];
             constexpr int S_END = M == 1 ? LOGR - 1 : LOGR;
+            if constexpr (M == 2)
+            {
+                // the non-lazy primes' schedule of the x reduction, carried on from the first phase
+                // (fparith.h fp_sched_reduce): the last stage reduces
+                stage_for<LOGE, S_END>([&](auto sc) {
+                    constexpr int s = decltype(sc)::value;
+                    ar.template fwd_tab_sched<E, fp_sched_reduce(s - LOGR)>(
+                        v, 1 << (LOGR - 1 - s), tl, [&](int e) { return (1 << s) + ((E * t + e) >> (LOGR - s)); });
+                });
+            }
+            else
+            {
 #pragma unroll
-            for (int s = LOGE; s < S_END; s++)
-                ar.template fwd_tab<E>(v, 1 << (LOGR - 1 - s), tl,
-                                       [&](int e) { return (1 << s) + ((E * t + e) >> (LOGR - s)); });
+                for (int s = LOGE; s < S_END; s++)
+                    ar.template fwd_tab<E>(v, 1 << (LOGR - 1 - s), tl,
+                                           [&](int e) { return (1 << s) + ((E * t + e) >> (LOGR - s)); });
+            }
             if constexpr (M == 1)
             {
                 auto ix = [&](int e) { return (1 << (LOGR - 1)) + ((E * t + e) >> 1); };
@@ -1411,8 +1453,9 @@ __global__ __launch_bounds__(256, (FP && !MIX) ? MHE_MODUP_OCC : MHE_MODUP_OCC_I
                 if (f64)
                 {
                     // MHE_INTER_F64: the double itself, for the fused MAC's FP path -- the last
-                    // non-lazy butterfly's output (|v| <= 2q + 1, what that path's row stages take
-                    // between stages), or a lazy prime's centred residue
+                    // non-lazy butterfly's output (it reduced x: |v| <= 2.46q, what that path's first
+                    // row stage takes; fparith.h, "Scheduled reduction of x"), or a lazy prime's
+                    // centred residue
 #pragma unroll
                     for (int e = 0; e < E; e++)
                     {
@@ -1702,9 +1745,21 @@ __device__ __forceinline__ u32 twz(u32 k)
 
 // Forward stages [s0, s1) of the local 2^LOGR transform, twiddles from the block's LDS row
 // (entry (1 << s) + g, at slot twz(.), holds tw[((2^k1 + b) << s) + g]).
-template <int LOGR, class A>
-__device__ __forceinline__ void row_stages(typename A::T (&v)[8], u32 t, int b_lo, int s0, int s1,
-                                           const typename A::TW *twl, const A &ar, int /*deduce*/ = 0)
+// A non-lazy FP prime reduces x in the stages fp_sched_reduce names (fparith.h: the row pass starts
+// without, from the column pass's |w| <= 2.46q or a residue).
+template <int LOGR, int S0, int S1, class A>
+__device__ __forceinline__ void row_stages(typename A::T (&v)[8], u32 t, int b_lo, const typename A::TW *twl, const A &ar)
+{
+    stage_for<S0, S1>([&](auto sc) {
+        constexpr int s = decltype(sc)::value;
+        ar.template fwd_tab_sched<8, fp_sched_reduce(s)>(v, 1 << (LOGR - 1 - s - b_lo), twl, // gap in slot units
+                                                         [&](int e) { return twz((1u << s) + (lay(t, e, b_lo) >> (LOGR - s))); });
+    });
+}
+// The integer arithmetic's row stages [s0, s1): nothing to schedule.
+template <int LOGR>
+__device__ __forceinline__ void row_stages_u(u64 (&v)[8], u32 t, int b_lo, int s0, int s1, const Tw *twl,
+                                             const NttArith<false> &ar)
 {
 #pragma unroll
     for (int s = s0; s < s1; s++)
@@ -1712,14 +1767,15 @@ __device__ __forceinline__ void row_stages(typename A::T (&v)[8], u32 t, int b_l
                                [&](int e) { return twz((1u << s) + (lay(t, e, b_lo) >> (LOGR - s))); });
 }
 // row_stages of two batch entries' vectors of one tile: every twiddle is read from LDS once
-template <int LOGR, class A>
-__device__ __forceinline__ void row_stages2(typename A::T (&v0)[8], typename A::T (&v1)[8], u32 t, int b_lo, int s0,
-                                            int s1, const typename A::TW *twl, const A &ar)
+template <int LOGR, int S0, int S1, class A>
+__device__ __forceinline__ void row_stages2(typename A::T (&v0)[8], typename A::T (&v1)[8], u32 t, int b_lo,
+                                            const typename A::TW *twl, const A &ar)
 {
-#pragma unroll
-    for (int s = s0; s < s1; s++)
-        ar.template fwd_tab2<8>(v0, v1, 1 << (LOGR - 1 - s - b_lo), twl,
-                                [&](int e) { return twz((1u << s) + (lay(t, e, b_lo) >> (LOGR - s))); });
+    stage_for<S0, S1>([&](auto sc) {
+        constexpr int s = decltype(sc)::value;
+        ar.template fwd_tab2_sched<8, fp_sched_reduce(s)>(v0, v1, 1 << (LOGR - 1 - s - b_lo), twl,
+                                                          [&](int e) { return twz((1u << s) + (lay(t, e, b_lo) >> (LOGR - s))); });
+    });
 }
 
 // waves per SIMD the FP64 fused MAC at n = 2^16 is compiled for: 168 VGPRs, one LDS transpose buffer
@@ -1966,6 +2022,8 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8 && NE == 1) ? MHE_KS_
                     {
                         double dv[NE];
 #pragma unroll
+                        // (non-lazy: the row pass's |d| <= 3.88q < 2^53 reduced to within q/2 + 2 <= 2^51,
+                        // fp_mulmod_gen's condition: fparith.h, "Scheduled reduction of x")
                         for (int x = 0; x < NE; x++) dv[x] = LZ ? d[x][e] : fp_reduce(d[x][e], ar.q, ar.qinv);
                         // canonical key residues
                         const double k0v = KF == 1 ? key_word_f(ka[e]) : fp_from_u52(ka[e]);
@@ -2003,7 +2061,8 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8 && NE == 1) ? MHE_KS_
                     {
                         // the column-pass output: FP and packed, a signed 48-bit residue (fp_to_s48 or
                         // fp_s48_of: |w| <= 2q + 1, inside what either butterfly takes); FP with
-                        // MHE_INTER_F64, the double itself (|w| <= 2q + 1 as well); otherwise canonical
+                        // MHE_INTER_F64, the double itself (a non-lazy prime's |w| <= 2.46q, what the
+                        // scheduled first stage takes: fparith.h); otherwise canonical
                         if constexpr (FPA && IF == 2)
                             w[x][e] = __longlong_as_double((long long)vin[x][e]);
                         else if constexpr (FPA)
@@ -2012,12 +2071,22 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8 && NE == 1) ? MHE_KS_
                             w[x][e] = ar.in52(vin[x][e]);
                     }
                 // forward stages [s0, s1) of every entry's vector, each twiddle read once
-                auto stages = [&](int b_lo, int first, int end) {
-                    if constexpr (NE == 2 && FPA) // (the integer arithmetic never runs with NE = 2)
-                        row_stages2<LOGR>(w[0], w[1], t, b_lo, first, end, mytw, ar);
-                    else
-                        row_stages<LOGR>(w[0], t, b_lo, first, end, mytw, ar);
+                // (the FP arithmetic takes the stage indices as constants: its schedule of the x
+                // reduction is chosen per stage at compile time)
+                auto stages_u = [&](int b_lo, int first, int end) {
+                    if constexpr (!FPA) row_stages_u<LOGR>(w[0], t, b_lo, first, end, mytw, ar);
                 };
+                auto stages_f = [&](int b_lo, auto first, auto end) {
+                    constexpr int S0 = decltype(first)::value, S1 = decltype(end)::value;
+                    if constexpr (FPA && NE == 2)
+                        row_stages2<LOGR, S0, S1>(w[0], w[1], t, b_lo, mytw, ar);
+                    else if constexpr (FPA)
+                        row_stages<LOGR, S0, S1>(w[0], t, b_lo, mytw, ar);
+                };
+                using C0 = std::integral_constant<int, 0>;
+                using C3 = std::integral_constant<int, 3>;
+                using C6 = std::integral_constant<int, 6>;
+                using CR = std::integral_constant<int, LOGR>;
                 // LDS slots of the transposes: swz is linear over GF(2) and lay(t, e, b) is the
                 // disjoint OR of a lane part and e << b, so slot = swz(lane part) ^ swz(e << b).  The
                 // non-lazy sweep (more live values) recomputes the XORs from three per-lane bases
@@ -2026,7 +2095,8 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8 && NE == 1) ? MHE_KS_
                 u32 sa = swz(lay(t, 0, B_A)), sb = swz(lay(t, 0, B_B)), s0 = swz(lay(t, 0, 0));
                 if constexpr (!LZ) asm volatile("" : "+v"(sa), "+v"(sb), "+v"(s0));
                 auto slot = [&](u32 lane_part, int e, int b) { return lane_part ^ swz((u32)e << b); };
-                stages(B_A, 0, 3);
+                if constexpr (FPA) stages_f(B_A, C0{}, C3{});
+                else stages_u(B_A, 0, 3);
                 wave_lds_fence(); // the previous digit's reads of x0 come first
 #pragma unroll
                 for (int x = 0; x < NE; x++)
@@ -2037,7 +2107,8 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8 && NE == 1) ? MHE_KS_
                 for (int x = 0; x < NE; x++)
 #pragma unroll
                     for (int e = 0; e < 8; e++) w[x][e] = x0[x][slot(sb, e, B_B)];
-                stages(B_B, 3, 6);
+                if constexpr (FPA) stages_f(B_B, C3{}, C6{});
+                else stages_u(B_B, 3, 6);
                 if (LOGR > 6)
                 {
                     wave_lds_fence();
@@ -2050,7 +2121,8 @@ __global__ __launch_bounds__(256, (FP && !MIX && LOGR == 8 && NE == 1) ? MHE_KS_
                     for (int x = 0; x < NE; x++)
 #pragma unroll
                         for (int e = 0; e < 8; e++) w[x][e] = x1[x][slot(s0, e, 0)];
-                    stages(0, 6, LOGR);
+                    if constexpr (FPA) stages_f(0, C6{}, CR{});
+                    else stages_u(0, 6, LOGR);
                 }
                 // already the keys' layout (integer: canonical digits keep the 128-bit sums
                 // exact for any digit count below 2^8)
