@@ -697,3 +697,211 @@ struct JobStrided
                      run_if && !*run_if };
     }
 };
+
+// ------------------------------------------------------------------------- batched encryption
+// Public-key encryption (encrypt.h; rlwe.cpp:220-286 followed by the rescale of util/rns.cpp:737-808)
+// at m = L + 1 limbs, dropped prime q_L.  The samples u, e_0, e_1 are planes of one signed byte per
+// coefficient (sample.hip k_enc_*), expanded to residues where a job reads them.  With uh = NTT(u),
+//     last_j    = INTT_L(uh_L pk_{j,L}) + e_j                        (mod q_L, canonical)
+//     out_{j,i} = (uh_i pk_{j,i} + NTT_i(e_j - r_{j,i})) q_L^-1       (mod q_i), i < L,
+// r_{j,i} the rescale lift of last_j; plain_i is added to out_{0,i} when the entry has a plaintext.
+
+// Coefficient x of a byte plane: the dword that holds it (four neighbouring lanes read the same one,
+// one request per four coefficients) and its byte.
+__device__ __forceinline__ int small_at(const u32 *plane, u32 x)
+{
+    return (int)(signed char)(plane[x >> 2] >> (8 * (x & 3)));
+}
+__device__ __forceinline__ u64 small_residue(int v, u64 q)
+{
+    return v >= 0 ? (u64)v : q - (u64)(-v);
+}
+
+// Forward NTT of u, column pass: job l expands u to prime l and writes uh[l] (the row pass is
+// JobFwdPlain on uh in place, canonical).
+struct JobEncU
+{
+    const u32 *u; // [n] bytes
+    u64 *uh;      // [m][n]
+    const PrimeDev *primes;
+    const Tw *tw;
+    int log_n;
+    struct View
+    {
+        const u32 *u;
+        u64 *dst;
+        PrimeDev p;
+        const Tw *tw;
+        bool skip;
+        __device__ u64 load(u32 x) const { return small_residue(small_at(u, x), p.q); }
+        __device__ void store(u32 x, u64 v) const { dst[x] = v; }
+    };
+    __device__ View view(int l) const
+    {
+        return View{ u, uh + ((size_t)l << log_n), prime_at(primes, l), tw + ((size_t)l << log_n), false };
+    }
+};
+
+// Inverse NTT of the dropped limb, job j = poly.  ROW (first pass): loads uh_L pk_{j,L}, stores lazy
+// into last[j]; !ROW (column pass, in place): its store adds e_j and canonicalises.
+template <bool ROW>
+struct JobEncLast
+{
+    const u64 *uh;  // [m][n]
+    const u64 *pk;  // [2][key_limbs][n]
+    const u32 *e;   // [2][n] bytes
+    u64 *last;      // [2][n]
+    const PrimeDev *primes;
+    const Tw *itw;
+    int L, key_limbs, log_n;
+    int fp = 0;
+    struct View
+    {
+        const u64 *a, *b;
+        const u32 *e;
+        u64 *dst;
+        PrimeDev p;
+        const Tw *tw;
+        bool skip, fp;
+        PrimeF f;
+        __device__ u64 load(u32 x) const
+        {
+            if (!ROW) return dst[x];
+            if (fp) // canonical operands below 2^51: the product within 1.25q, canonicalised
+                return fp_canon(fp_mulmod_gen(fp_from_u52(a[x]), fp_from_u52(b[x]), f.pd, f.pi), f.pd, f.pi);
+            return mulmod(a[x], b[x], p);
+        }
+        __device__ void store(u32 x, u64 v) const
+        {
+            if (ROW)
+            {
+                dst[x] = v;
+                return;
+            }
+            const int s = small_at(e, x);      // ahead of the arithmetic on v
+            v = csub(v, p.q);                  // [0, 2q) (canonical in FP) -> canonical
+            dst[x] = s >= 0 ? addmod(v, (u64)s, p.q) : submod(v, (u64)(-s), p.q);
+        }
+    };
+    __device__ View view(int j) const
+    {
+        View v;
+        v.a = uh + ((size_t)L << log_n);
+        v.b = pk + ((size_t)(j * key_limbs + L) << log_n);
+        v.e = e + ((size_t)j << (log_n - 2));
+        v.dst = last + ((size_t)j << log_n);
+        v.p = prime_at(primes, L);
+        v.tw = itw + ((size_t)L << log_n);
+        v.skip = false;
+        v.fp = fp != 0;
+        v.f = prime_f(v.p);
+        return v;
+    }
+};
+
+// Lift column pass: job y = j*L + i loads e_j - r_{j,i} (JobRescaleCol's lift of last_j, taken from
+// the expanded error) and starts its NTT mod q_i.
+struct JobEncLiftCol
+{
+    const u64 *last; // [2][n] canonical mod q_L
+    const u32 *e;    // [2][n] bytes
+    u64 *scratch;    // [2][L][n]
+    const PrimeDev *primes;
+    const Tw *tw;
+    int L, log_n;
+    int fp = 0;
+    struct View : LiftColView<RescaleLift>
+    {
+        const u32 *e;
+        bool fp;
+        PrimeF f;
+        __device__ u64 load(u32 x) const
+        {
+            const u64 s = src[x];
+            const int v = small_at(e, x);
+            if (fp) // |e - lift_c| <= q_L/2 + 21 < 2^51: one canonicalisation
+                return fp_canon((double)v - lift_c(s), f.pd, f.pi);
+            return small_residue(v, p.q) + p.two_q - lift(s); // the lift in [0, 2q): (0, 3q], a forward input
+        }
+    };
+    __device__ View view(int y) const
+    {
+        const int j = y / L, i = y % L;
+        const PrimeDev p = prime_at(primes, i);
+        return View{ { last + ((size_t)j << log_n), scratch + ((size_t)y << log_n), p, rescale_lift(primes, i, L + 1),
+                       tw + ((size_t)i << log_n), false },
+                     e + ((size_t)j << (log_n - 2)), fp != 0, prime_f(p) };
+    }
+};
+
+// Row pass: out[j][i] = (uh_i pk_{j,i} + t) q_L^-1 (+ plain_i for j = 0), t the transform of the lift
+// column pass.  The product is formed in pre(), with the pass's own loads.
+struct JobEncRow
+{
+    u64 *scratch;     // [2][L][n]
+    const u64 *uh;    // [m][n] canonical
+    const u64 *pk;    // [2][key_limbs][n]
+    const u64 *plain; // [L][n] or null
+    u64 *out;         // [2][L][n]
+    const PrimeDev *primes;
+    const Tw *tw;
+    const Tw *invq;
+    int L, K, key_limbs, log_n;
+    int fp = 0; // every prime < 2^51: the epilogue in exact FP64 (fparith.h)
+    struct View
+    {
+        u64 *buf;
+        const u64 *up, *kp, *mp;
+        u64 *outp;
+        PrimeDev p;
+        const Tw *tw;
+        Tw inv;
+        bool skip, fp;
+        PrimeF f;
+        double invd;
+        __device__ u64 load(u32 x) const { return buf[x]; }
+        struct Pre
+        {
+            u64 a, m; // uh pk: a double's bits within 1.25q (FP) or the canonical residue; the plaintext word
+        };
+        __device__ Pre pre(u32 x) const
+        {
+            const u64 u = up[x], k = kp[x], m = mp ? mp[x] : 0;
+            if (fp)
+                return Pre{ (u64)__double_as_longlong(fp_mulmod_gen(fp_from_u52(u), fp_from_u52(k), f.pd, f.pi)), m };
+            return Pre{ mulmod(u, k, p), m };
+        }
+        __device__ void store(u32 x, u64 t, Pre o) const
+        {
+            if (fp)
+            {
+                // t canonical: the sum within 2.25q < 2^53, its centred residue times q_L^-1 within
+                // 1.25q, plus m < q, one canonicalisation: the residue of the integer form
+                const double s = fp_reduce(__longlong_as_double((long long)o.a) + fp_from_u52(t), f.pd, f.pi);
+                outp[x] = fp_canon(fp_mulmod_gen(s, invd, f.pd, f.pi) + fp_from_u52(o.m), f.pd, f.pi);
+                return;
+            }
+            const u64 v = mul_shoup(o.a + t, inv.x, inv.y, p.q); // t in [0, 4q): the sum below 5q
+            outp[x] = addmod(v, o.m, p.q);
+        }
+        __device__ void store(u32 x, u64 t) const { store(x, t, pre(x)); }
+    };
+    __device__ View view(int y) const
+    {
+        const int j = y / L, i = y % L;
+        View v;
+        v.buf = scratch + ((size_t)y << log_n);
+        v.up = uh + ((size_t)i << log_n);
+        v.kp = pk + ((size_t)(j * key_limbs + i) << log_n);
+        v.mp = (j == 0 && plain) ? plain + ((size_t)i << log_n) : nullptr;
+        v.outp = out + ((size_t)y << log_n);
+        v.p = prime_at(primes, i);
+        v.tw = tw + ((size_t)i << log_n);
+        v.inv = tw_at(invq, (size_t)L * K + i);
+        v.skip = false;
+        v.fp = fp != 0;
+        v.f = prime_f(v.p);
+        v.invd = (double)v.inv.x;
+        return v;
+    }
+};

@@ -310,6 +310,7 @@ struct mhe_ctx
     std::atomic<unsigned long long> hoist_rot{ 0 }, hoist_mac{ 0 }, hoist_bad{ 0 }; // mhe_hoist_stats
     std::atomic<unsigned long long> rotsum_sums{ 0 }, rotsum_terms{ 0 };             // mhe_rotsum_stats
     std::atomic<unsigned long long> prodsum_sums{ 0 }, prodsum_terms{ 0 };           // mhe_prodsum_stats
+    std::atomic<unsigned long long> enc_entries{ 0 }, enc_groups{ 0 };               // mhe_encrypt_stats
     std::atomic<int> fail_alloc{ 0 }; // mhe_debug_fail_alloc: the n-th next allocation fails (0: off)
     TwF *cmodf = nullptr; // [K][K]: (q_j mod q_i, (q_j mod q_i) / q_i) as doubles, j major (hoist.h)
     std::mutex mask_mu;
@@ -1746,6 +1747,9 @@ MHE_EXPORT int mhe_apply_galois_to(mhe_ctx *c, const uint64_t *in, uint64_t *out
 
 // ------------------------------------------------- sums of relinearized products, rescaled
 #include "prodsum.h"
+
+// ------------------------------------------------------- public-key encryption of a batch
+#include "encrypt.h"
 
 MHE_EXPORT int mhe_rescale_batch(mhe_ctx *c, int count, const uint64_t *const *in, uint64_t *const *out, int size,
                                  int limbs, void *s)

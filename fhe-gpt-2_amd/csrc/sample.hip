@@ -18,7 +18,8 @@
 //     on the stream, no host round trip.
 //   sample_poly_cbd (rlwe.cpp:101-133): 6 bytes per coefficient, x[2], x[5] masked to 5 bits,
 //     noise = pop(x0)+pop(x1)+pop(x2) - pop(x3)-pop(x4)-pop(x5).
-// Small samples are written as canonical residues over every requested limb (rand + (flag & q)).
+// Small samples are written as canonical residues over every requested limb (rand + (flag & q));
+// the batched encryption's samplers (k_enc_*) write one signed byte per coefficient instead.
 #include <hip/hip_runtime.h>
 
 #include "../../include/mhe.h"
@@ -246,6 +247,117 @@ __global__ __launch_bounds__(256) void k_prng_cbd(Seed s, u64 off, const u32 *ex
     }
 }
 
+// ------------------------------------------------------------------ batched encryption samples
+// The three small polys of a public-key encryption (encrypt_zero_asymmetric, rlwe.cpp:220-286) for a
+// batch of entries, one signed byte per coefficient: small[entry][3][n], entries `pitch` bytes apart,
+// = u (ternary, stream byte 0), e_0 and e_1 (CBD, bytes 4n and 10n plus what the entry's ternary
+// redraws consumed).  The residues
+// mod each prime are expanded where they are used (jobs.h, the encryption jobs).  The entry comes
+// from the grid; its seed and its redraw state[entry][2] (as k_prng_ternary's) are its own.
+constexpr int MHE_SAMPLE_MAXB = 8; // entries per launch: ntt.h MHE_MAXB (encrypt.h asserts it fits)
+struct SeedB
+{
+    Seed s[MHE_SAMPLE_MAXB];
+};
+
+// k_prng_ternary for entry blockIdx.y: a thread's 16 values leave as one 16-byte store.
+__global__ __launch_bounds__(256) void k_enc_ternary(SeedB sb, signed char *small, size_t pitch, int log_n, u32 *state)
+{
+    __shared__ u64 roots[kMaxRoots][8];
+    const int ent = blockIdx.y;
+    const u64 n = (u64)1 << log_n;
+    const u64 nblk = n / 16, wb0 = (u64)blockIdx.x * 256;
+    const u64 wg_end = (wb0 + 256 < nblk ? wb0 + 256 : nblk);
+    load_roots(sb.s[ent], wb0 >> 6, (int)(((wg_end - 1) >> 6) - (wb0 >> 6) + 1), roots);
+    if (wb0 + threadIdx.x >= wg_end) return;
+    u64 w[8];
+    block_from_roots(roots, wb0 >> 6, wb0 + threadIdx.x, w);
+    u32 pk[4] = { 0, 0, 0, 0 }, zeros = 0;
+#pragma unroll
+    for (int k = 0; k < 16; k++)
+    {
+        const u32 g = (u32)(w[k >> 1] >> (32 * (k & 1)));
+        zeros += g == 0;
+        const u32 v = (u32)(((u64)g * 3) >> 32) - 1u; // {0, 1, 2} -> {-1, 0, 1}
+        pk[k >> 2] |= (v & 0xffu) << (8 * (k & 3));
+    }
+    if (zeros) atomicAdd(&state[2 * ent + 1], zeros);
+    uint4 *o = reinterpret_cast<uint4 *>(small + (size_t)ent * pitch) + wb0 + threadIdx.x;
+    *o = make_uint4(pk[0], pk[1], pk[2], pk[3]);
+}
+
+// k_prng_ternary_fix per entry (workgroup = entry): returns at once for an entry without a zero word.
+__global__ void k_enc_ternary_fix(SeedB sb, signed char *small, size_t pitch, int log_n, u32 *state)
+{
+    const int ent = blockIdx.x;
+    if (threadIdx.x != 0) return;
+    if (state[2 * ent + 1] == 0)
+    {
+        state[2 * ent] = 0;
+        return;
+    }
+    const u64 n = (u64)1 << log_n;
+    signed char *o = small + (size_t)ent * pitch;
+    u64 pos = 0, cached = ~0ULL, w[8];
+    for (u64 i = 0; i < n; i++)
+    {
+        u32 g;
+        do
+        {
+            const u64 blk = pos >> 6;
+            if (blk != cached)
+            {
+                stream_block(sb.s[ent], blk, w);
+                cached = blk;
+            }
+            g = (u32)(w[(pos & 63) >> 3] >> (32 * ((pos >> 2) & 1)));
+            pos += 4;
+        } while (g == 0);
+        o[i] = (signed char)((int)(((u64)g * 3) >> 32) - 1);
+    }
+    state[2 * ent] = (u32)(pos - 4 * n);
+}
+
+// k_prng_cbd for error poly j = blockIdx.y of entry blockIdx.z, from byte 4n + 6n j + the entry's
+// extra bytes: a thread's 4 noise values leave as one dword.
+__global__ __launch_bounds__(256) void k_enc_cbd(SeedB sb, signed char *small, size_t pitch, int log_n, const u32 *state)
+{
+    __shared__ u64 roots[kMaxRoots][8];
+    __shared__ u64 bytes[kCbdBlocks * 8];
+    const int j = blockIdx.y, ent = blockIdx.z;
+    const u64 n = (u64)1 << log_n;
+    const u64 c0 = (u64)blockIdx.x * kCbdCoeffs;
+    const u64 cnt = (n - c0) < (u64)kCbdCoeffs ? (n - c0) : (u64)kCbdCoeffs; // a multiple of 4
+    const u64 start = 4 * n + 6 * n * (u64)j + state[2 * ent] + 6 * c0;
+    const u64 b0 = start >> 6, b1 = (start + 6 * cnt - 1) >> 6;
+    load_roots(sb.s[ent], b0 >> 6, (int)((b1 >> 6) - (b0 >> 6) + 1), roots);
+    if (threadIdx.x <= b1 - b0)
+    {
+        u64 w[8];
+        block_from_roots(roots, b0 >> 6, b0 + threadIdx.x, w);
+#pragma unroll
+        for (int k = 0; k < 8; k++) bytes[threadIdx.x * 8 + k] = w[k];
+    }
+    __syncthreads();
+    const u32 skip = (u32)(start - 64 * b0);
+    auto byte_at = [&](u32 i) -> u32 {
+        i += skip;
+        return (u32)(bytes[i >> 3] >> (8 * (i & 7))) & 0xff;
+    };
+    if (4 * threadIdx.x >= cnt) return;
+    u32 pk = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+    {
+        const u32 c = 6 * (4 * threadIdx.x + k);
+        const int v = __popc(byte_at(c)) + __popc(byte_at(c + 1)) + __popc(byte_at(c + 2) & 0x1f) -
+                      __popc(byte_at(c + 3)) - __popc(byte_at(c + 4)) - __popc(byte_at(c + 5) & 0x1f);
+        pk |= ((u32)v & 0xffu) << (8 * k);
+    }
+    u32 *o = reinterpret_cast<u32 *>(small + (size_t)ent * pitch + (size_t)(1 + j) * n + c0);
+    o[threadIdx.x] = pk;
+}
+
 int launch_check(const char *what)
 {
     if (hipGetLastError() != hipSuccess) return mhe_internal_fail(MHE_ERR_DEVICE, what);
@@ -254,6 +366,33 @@ int launch_check(const char *what)
 } // namespace
 
 #define MHE_EXPORT extern "C" __attribute__((visibility("default")))
+
+// The samples of B <= MHE_SAMPLE_MAXB encryptions (encrypt.h): small [B][3][n] signed bytes, entry e at
+// small + e * pitch (both multiples of 16), state [B][2] device words.  Three launches and one memset,
+// no host synchronisation.
+int mhe_internal_encrypt_samples(mhe_ctx *c, int B, const uint64_t (*seeds)[8], signed char *small, uint32_t *state,
+                                 size_t pitch, hipStream_t st)
+{
+    const PrimeDev *primes;
+    const uint64_t *q;
+    int K, log_n;
+    if (mhe_internal_primes(c, &primes, &q, &K, &log_n)) return mhe_internal_fail(MHE_ERR_ARG, "context is not valid");
+    if (!seeds || !small || !state || B < 1 || B > MHE_SAMPLE_MAXB || log_n < 5 || (((uintptr_t)small | pitch) & 15) ||
+        (B > 1 && pitch < 3 * ((size_t)1 << log_n)))
+        return mhe_internal_fail(MHE_ERR_ARG, "invalid sampling arguments");
+    SeedB sb{};
+    for (int e = 0; e < B; e++)
+        for (int i = 0; i < 8; i++) sb.s[e].w[i] = seeds[e][i];
+    const u64 n = (u64)1 << log_n;
+    if (hipMemsetAsync(state, 0, 8 * (size_t)B, st) != hipSuccess)
+        return mhe_internal_fail(MHE_ERR_DEVICE, "sampling state reset failed");
+    hipLaunchKernelGGL(k_enc_ternary, dim3((unsigned)((n / 16 + 255) / 256), (unsigned)B), dim3(256), 0, st, sb, small,
+                       pitch, log_n, state);
+    hipLaunchKernelGGL(k_enc_ternary_fix, dim3((unsigned)B), dim3(64), 0, st, sb, small, pitch, log_n, state);
+    hipLaunchKernelGGL(k_enc_cbd, dim3((unsigned)((n + kCbdCoeffs - 1) / kCbdCoeffs), 2, (unsigned)B), dim3(256), 0, st,
+                       sb, small, pitch, log_n, (const u32 *)state);
+    return launch_check("sampling kernel launch failed");
+}
 
 MHE_EXPORT int mhe_prng_uniform_bulk(mhe_ctx *c, const uint64_t seed[8], int limbs, const int *prime_of_limb,
                                      const int *slot_of_limb, uint64_t *out, uint64_t *rej, uint32_t *rej_count,

@@ -723,8 +723,21 @@ public:
     void encrypt_zero_symmetric(parms_id_type parms_id, Ciphertext &destination, MemoryPoolHandle = {}) const;
     Serializable<Ciphertext> encrypt_zero_symmetric(MemoryPoolHandle = {}) const;
     Serializable<Ciphertext> encrypt_zero_symmetric(parms_id_type parms_id, MemoryPoolHandle = {}) const;
+    // (not SEAL API) encrypt(*plains[i], *destinations[i]) / encrypt_zero(parms_id, *destinations[i])
+    // for every i, the plaintexts all at one level and in NTT form, the destinations distinct: one
+    // batched device encryption (mhe_encrypt_pk_batch) instead of a launch sequence per ciphertext.
+    // One seed is drawn per entry, in order, so the words, scales and parms_ids are those of the same
+    // sequence of single calls.  Throws as encrypt does ("plain must be in NTT form", "plain is not
+    // valid for encryption parameters", logic_error "public key is not set"); the results go to fresh
+    // ciphertexts, so when a call throws no destination has changed.  With
+    // set_batched_launches(false) or under MHE_EVAL_TRACE it calls encrypt / encrypt_zero per entry,
+    // into fresh ciphertexts as well.  Never synchronises.
+    void encrypt_many(const std::vector<const Plaintext *> &plains, const std::vector<Ciphertext *> &destinations) const;
+    void encrypt_zero_many(parms_id_type parms_id, const std::vector<Ciphertext *> &destinations) const;
 
 private:
+    void encrypt_batch(parms_id_type parms_id, const std::vector<const Plaintext *> *plains,
+                       const std::vector<Ciphertext *> &destinations) const;
     // symmetric: secret key; public_seed (symmetric only) receives c1's PRNG seed
     void encrypt_zero_at(std::size_t limbs, Ciphertext &dest, bool symmetric,
                          prng_seed_type *public_seed = nullptr) const;

@@ -121,6 +121,9 @@ SIGNATURES = {
     "mhe_prng_uniform_bulk": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_uint32, vp]),
     "mhe_prng_apply_fixes": (ctypes.c_int, [vp, vp, ctypes.c_uint32, vp, vp]),
     "mhe_prng_small": (ctypes.c_int, [vp, vp, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, vp, vp, vp]),
+    "mhe_encrypt_pk_batch": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp, ctypes.c_int, vp]),
+    "mhe_encrypt_stats": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                         ctypes.c_int]),
 }
 
 
@@ -531,6 +534,26 @@ class Engine:
         s, t = ctypes.c_uint64(), ctypes.c_uint64()
         _check(lib().mhe_prodsum_stats(self._h, ctypes.byref(s), ctypes.byref(t), 1 if reset else 0))
         return s.value, t.value
+
+    def encrypt_pk_batch(self, seeds, pk, plains, L, outs=None, key_limbs=None):
+        """mhe_encrypt_pk_batch: outs[i] [2][L][n] = the public-key encryption (Encryptor::encrypt /
+        encrypt_zero) drawn from Blake2xbPRNG(seeds[i]) under pk [2][key_limbs][n], plus plains[i]
+        [L][n] on poly 0 where it is not None (plains None: every entry encrypts zero) -- one
+        launch sequence per 8 entries, the samples kept as bytes."""
+        cnt = len(seeds)
+        sd = np.ascontiguousarray(np.array(seeds, np.uint64).reshape(cnt, 8))
+        outs = [self.empty(2, L, self.n) for _ in range(cnt)] if outs is None else outs
+        pl = None if plains is None else (ctypes.c_void_p * cnt)(*[None if p is None else p.data_ptr() for p in plains])
+        kl = pk.shape[1] if key_limbs is None else int(key_limbs)
+        _check(lib().mhe_encrypt_pk_batch(self._h, cnt, sd.ctypes.data_as(ctypes.c_void_p), _ptr(pk), kl, pl,
+                                          self._ptrs(outs), L, self.stream()))
+        return outs
+
+    def encrypt_stats(self, reset=False):
+        """mhe_encrypt_stats: (entries, launch groups) that took encrypt_pk_batch's fused path."""
+        e, g = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().mhe_encrypt_stats(self._h, ctypes.byref(e), ctypes.byref(g), 1 if reset else 0))
+        return e.value, g.value
 
     def rescale_batch(self, cts, outs=None):
         size, L = cts[0].shape[0], cts[0].shape[1]

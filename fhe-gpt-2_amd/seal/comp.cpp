@@ -14,6 +14,7 @@
 #include <stdexcept>
 
 #include "mhe_cnn.h" // pow2, log2 helpers
+#include "trace.h"
 
 namespace
 {
@@ -236,12 +237,13 @@ void eval_polynomial_integrate(Encryptor &encryptor, Evaluator &evaluator, Decry
     std::vector<std::unique_ptr<Ciphertext>> T(100), pt(100);
     Ciphertext temp1, ctxt_zero;
 
-    // Enc(0) at scale^2 (lazy scaling) for the baby variant
-    {
-        Plaintext plain_zero;
-        encoder.encode(std::vector<double>(n, 0.0), scale * scale, plain_zero);
-        encryptor.encrypt(plain_zero, ctxt_zero);
-    }
+    // Enc(0) at scale^2 (lazy scaling) for the baby variant.  It and T0 = Enc(1) below are drawn back
+    // to back with nothing random between them, so with batched launches they are one encrypt_many
+    // (the same two seeds in the same order: the same words); a traced run keeps its record order.
+    const bool enc_pair = batched_launches() && !trace::enabled();
+    Plaintext plain_zero;
+    encoder.encode(std::vector<double>(n, 0.0), scale * scale, plain_zero);
+    if (!enc_pair) encryptor.encrypt(plain_zero, ctxt_zero);
     long temp_index = tree.type == evaltype::oddbaby ? 1 : 0;
     for (long i = 1; i < nodes; i++)
         if (tree.tree[i] == 0)
@@ -256,7 +258,11 @@ void eval_polynomial_integrate(Encryptor &encryptor, Evaluator &evaluator, Decry
     {
         Plaintext plain_1;
         encoder.encode(std::vector<double>(n, 1.0), scale, plain_1);
-        encryptor.encrypt(plain_1, *T[0]);
+        if (enc_pair)
+            encryptor.encrypt_many({ &plain_zero, &plain_1 }, { &ctxt_zero, T[0].get() });
+        else
+            encryptor.encrypt(plain_1, *T[0]);
+        plain_zero = Plaintext(); // as short-lived as plain_1
     }
     auto need = [](const std::unique_ptr<Ciphertext> &p, const char *what) -> Ciphertext & {
         if (!p) throw std::runtime_error(std::string(what) + " is not set");

@@ -419,6 +419,86 @@ void Encryptor::encrypt_plain(const Plaintext &plain, Ciphertext &destination, b
     destination.scale() = plain.scale();
 }
 
+// The batch behind encrypt_many (plains given) and encrypt_zero_many (plains null), all at parms_id.
+void Encryptor::encrypt_batch(parms_id_type parms_id, const std::vector<const Plaintext *> *plains,
+                              const std::vector<Ciphertext *> &destinations) const
+{
+    const std::size_t B = destinations.size();
+    if (plains && plains->size() != B) throw std::invalid_argument("plains and destinations differ in number");
+    for (std::size_t i = 0; i < B; i++)
+    {
+        if (!destinations[i] || (plains && !(*plains)[i]))
+            throw std::invalid_argument("plains and destinations cannot be null");
+        for (std::size_t j = 0; j < i; j++)
+            if (destinations[j] == destinations[i]) throw std::invalid_argument("destinations must be distinct");
+    }
+    for (std::size_t i = 0; plains && i < B; i++)
+    {
+        const Plaintext &plain = *(*plains)[i];
+        if (!plain.is_ntt_form()) throw std::invalid_argument("plain must be in NTT form");
+        if (!ctx_.get_context_data(plain.parms_id()))
+            throw std::invalid_argument("plain is not valid for encryption parameters");
+        if (plain.parms_id() != parms_id) throw std::invalid_argument("plains must be at one level");
+    }
+    auto cd = ctx_.get_context_data(parms_id);
+    if (!cd) throw std::invalid_argument("parms_id is not valid for encryption parameters");
+    if (!asymmetric_) throw std::logic_error("public key is not set");
+    if (!B) return;
+    // fresh ciphertexts: the destinations change only when every entry has been issued
+    std::vector<Ciphertext> fresh(B);
+    if (!batched_launches() || trace::enabled())
+    {
+        // entry by entry (a trace keeps one record per entry), as encode_each does
+        for (std::size_t i = 0; i < B; i++)
+        {
+            if (plains)
+                encrypt(*(*plains)[i], fresh[i]);
+            else
+                encrypt_zero(parms_id, fresh[i]);
+        }
+    }
+    else
+    {
+        const std::size_t L = cd->parms().coeff_modulus().size(), K = ctx_.key_size();
+        void *s = ctx_.stream();
+        std::vector<prng_seed_type> seeds(B);
+        std::vector<const std::uint64_t *> in(B, nullptr);
+        std::vector<std::uint64_t *> out(B);
+        static_assert(sizeof(prng_seed_type) == 8 * sizeof(std::uint64_t), "a seed is eight words");
+        for (std::size_t i = 0; i < B; i++)
+        {
+            seeds[i] = rng_->next_seed(); // one per entry, in order: the seeds of the single calls
+            fresh[i].resize(ctx_, parms_id, 2);
+            fresh[i].is_ntt_form() = true;
+            fresh[i].scale() = plains ? (*plains)[i]->scale() : 1.0;
+            out[i] = fresh[i].store().dev_write(s, true);
+            if (plains) in[i] = (*plains)[i]->store().dev_read(s);
+        }
+        chk(mhe_encrypt_pk_batch(ctx_.engine(), (int)B, reinterpret_cast<const std::uint64_t(*)[8]>(seeds.data()),
+                                 pk_.data().store().dev_read(s), (int)K, plains ? in.data() : nullptr, out.data(), (int)L,
+                                 s));
+    }
+    for (std::size_t i = 0; i < B; i++) *destinations[i] = std::move(fresh[i]);
+}
+
+void Encryptor::encrypt_many(const std::vector<const Plaintext *> &plains,
+                             const std::vector<Ciphertext *> &destinations) const
+{
+    parms_id_type id = ctx_.first_parms_id();
+    for (const Plaintext *p : plains)
+        if (p)
+        {
+            id = p->parms_id();
+            break;
+        }
+    encrypt_batch(id, &plains, destinations);
+}
+
+void Encryptor::encrypt_zero_many(parms_id_type parms_id, const std::vector<Ciphertext *> &destinations) const
+{
+    encrypt_batch(parms_id, nullptr, destinations);
+}
+
 // ------------------------------------------------------------------------------ Decryptor
 Decryptor::Decryptor(const SEALContext &context, const SecretKey &secret_key) : ctx_(context), sk_(secret_key)
 {

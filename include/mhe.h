@@ -461,6 +461,32 @@ int mhe_prng_apply_fixes(mhe_ctx *ctx, const uint64_t *fixes_dev, uint32_t count
 #define MHE_SAMPLE_CBD 3
 int mhe_prng_small(mhe_ctx *ctx, const uint64_t seed[8], uint64_t byte_offset, int kind, int limbs, uint64_t *out,
                    uint32_t *state_dev, void *stream);
+/* Public-key encryption of a batch (no SEAL counterpart; Encryptor::encrypt / encrypt_zero entry by
+ * entry): out[i][2][L][n], L = limbs, holds the words of encrypt_zero_asymmetric (rlwe.cpp:220-286)
+ * drawn from Blake2xbPRNG(seeds[i]) in SEAL's stream order (u ternary at byte 0, e_0 CBD at 4n plus the
+ * bytes the ternary redraws consumed, e_1 at 10n plus the same) over primes 0..L with pk [2][key_limbs][n]
+ * restricted to limbs 0..L, divided and rounded by prime L (util/rns.cpp:737-808; the special prime when
+ * L = key_limbs - 1), plus plain[i][L][n] (NTT form) on poly 0 when plain[i] is not NULL.  plain may be
+ * NULL: every entry encrypts zero.  Word for word the sequence mhe_prng_small x 3, mhe_ntt_forward x 2,
+ * (mhe_multiply_plain, mhe_add) x 2, mhe_rescale_to_next, mhe_add of the plaintext.
+ * The identity: with uh = NTT(u), SEAL's c_j = uh pk_j + NTT(e_j) and out_{j,i} = (c_{j,i} -
+ * NTT_i(r_{j,i})) q_L^-1 with r_{j,i} the rescale lift of INTT(c_{j,L}); the NTT is linear mod q_i and
+ * e_j is drawn in coefficient form, so
+ *     last_j    = INTT_L(uh_L pk_{j,L}) + e_j                    (mod q_L)
+ *     out_{j,i} = (uh_i pk_{j,i} + NTT_i(e_j - r_{j,i})) q_L^-1   (mod q_i), i < L:
+ * one forward NTT per output limb, none of e_j, c never written, and the samples held as one signed
+ * byte per coefficient.
+ * key_limbs is the context's prime count (a public key lives at the key level); 1 <= limbs <=
+ * key_limbs - 1; count >= 1, more than 8 entries run in groups of 8; outputs disjoint from each
+ * other, from pk and from every plaintext.  All arguments are checked and all scratch is grown before
+ * the first launch: a failed call leaves every out[i] as it was.  Stream-ordered, no host
+ * synchronisation.  mhe_op_counts sees the sequence's op mix: per entry 3 NTTs, 2 plaintext products,
+ * 2 additions and 2 rescales at L + 1, and one addition at L for a plaintext.
+ * mhe_encrypt_stats: entries encrypted and launch groups issued by mhe_encrypt_pk_batch since the last
+ * reset. */
+int mhe_encrypt_pk_batch(mhe_ctx *ctx, int count, const uint64_t (*seeds)[8], const uint64_t *pk, int key_limbs,
+                         const uint64_t *const *plain, uint64_t *const *out, int limbs, void *stream);
+int mhe_encrypt_stats(mhe_ctx *ctx, uint64_t *entries, uint64_t *launch_groups, int reset);
 
 #ifdef __cplusplus
 }

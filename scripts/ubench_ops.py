@@ -9,6 +9,10 @@ mhe_rotate_sum.
 prodseqGxT / prodsumGxT (--ops prodseq,prodsum --prodsum GxT[d],...): G sums of T products, doubled with
 a trailing d -- mhe_ct_multiply, mhe_switch_key_batch, the mhe_adds and mhe_rescale_batch against
 mhe_ct_multiply and one mhe_relin_sum_rescale; words compared first, interleaved rounds (prod_bench).
+encseqB / encbatchB (--ops encrypt --encrypt B,...): B public-key encryptions with plaintexts -- per entry
+the sequence of Encryptor::encrypt (3 mhe_prng_small, 2 mhe_ntt_forward, 2 x (mhe_multiply_plain, mhe_add),
+mhe_rescale_to_next, mhe_add of the plaintext; buffers allocated once) against one mhe_encrypt_pk_batch;
+words compared first, interleaved rounds (enc_bench).
 Used for A/B runs of library variants (MHE_LIB_PATH=build/var/NAME/libmhe.so).
 
     python scripts/ubench_ops.py [--limbs 31] [--reps 50]
@@ -93,6 +97,65 @@ def prod_bench(eng, rnd, key, L, n, shape, reps, rounds, st):
                       "ratio": round(med["prodsum"] / med["prodseq"], 4)}), flush=True)
 
 
+def enc_bench(eng, rnd, L, n, B, reps, rounds, st):
+    """encseq against encbatch for B encryptions at L limbs (the dropped prime is prime L).  encseq is
+    the sequence Encryptor::encrypt issues per ciphertext, on buffers allocated once; encbatch one
+    mhe_encrypt_pk_batch.  The legs' words are compared first; then `rounds` interleaved rounds of HIP
+    events around `reps` calls after 3 warm-ups.  One JSON line per leg and round, then one with the
+    medians and each leg's spread (max - min over its rounds)."""
+    m, K = L + 1, eng.K
+    pk = rnd(2, K, n, limbs=K)
+    seeds = [[100 + i, 2, 3, 4, 5, 6, 7, 8] for i in range(B)]
+    plains = [rnd(L, n, limbs=L) for _ in range(B)]
+    u, e, c = eng.empty(m, n), eng.empty(2, m, n), eng.empty(2, m, n)
+    state = torch.zeros(2, dtype=torch.int32, device=eng.torch_device)
+    out_seq = [eng.empty(2, L, n) for _ in range(B)]
+    out_bat = [eng.empty(2, L, n) for _ in range(B)]
+
+    def encseq():
+        for i in range(B):
+            eng.prng_small("ternary", m, seeds[i], out=u, state=state)
+            eng.prng_small("cbd", m, seeds[i], 4 * n, out=e[0], state=state)
+            eng.prng_small("cbd", m, seeds[i], 10 * n, out=e[1], state=state)
+            eng.ntt_forward(u, lazy=True)
+            eng.ntt_forward(e, lazy=True)
+            for j in range(2):
+                eng.multiply_plain(u, pk[j, :m], out=c[j])
+                eng.add(e[j], c[j], out=c[j])
+            eng.rescale_to_next(c, out_seq[i])
+            eng.add(out_seq[i][0], plains[i], out=out_seq[i][0])
+
+    def encbatch():
+        eng.encrypt_pk_batch(seeds, pk, plains, L, outs=out_bat)
+
+    legs = {"encseq": encseq, "encbatch": encbatch}
+    encseq()
+    encbatch()
+    torch.cuda.synchronize()
+    if not all(torch.equal(x, y) for x, y in zip(out_seq, out_bat)):
+        raise SystemExit(f"encseq and encbatch differ at {B} entries, {L} limbs")
+    us = {k: [] for k in legs}
+    for r in range(rounds):
+        for name, f in legs.items():
+            for _ in range(3):
+                f()
+            torch.cuda.synchronize()
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record(st)
+            for _ in range(reps):
+                f()
+            t1.record(st)
+            torch.cuda.synchronize()
+            us[name].append(t0.elapsed_time(t1) * 1000 / reps)
+            print(json.dumps({"op": f"{name}{B}", "limbs": L, "round": r, "us": round(us[name][-1], 2)}), flush=True)
+    med = {k: float(np.median(v)) for k, v in us.items()}
+    print(json.dumps({"op": f"encrypt{B}", "limbs": L, "words_equal": True,
+                      "encseq_us": round(med["encseq"], 2), "encbatch_us": round(med["encbatch"], 2),
+                      "encseq_spread_us": round(max(us["encseq"]) - min(us["encseq"]), 2),
+                      "encbatch_spread_us": round(max(us["encbatch"]) - min(us["encbatch"]), 2),
+                      "ratio": round(med["encbatch"] / med["encseq"], 4)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--limbs", type=int, default=31)
@@ -104,7 +167,8 @@ def main():
     ap.add_argument("--prodsum", default="8x1,8x1d,1x8,4x2",
                     help="sums x products per sum of the prodseq / prodsum ops, comma-separated; a trailing d: doubled")
     ap.add_argument("--prod-reps", type=int, default=20, help="calls per timed round of prodseq / prodsum")
-    ap.add_argument("--rounds", type=int, default=3, help="interleaved rounds of prodseq / prodsum")
+    ap.add_argument("--rounds", type=int, default=3, help="interleaved rounds of prodseq / prodsum / encrypt")
+    ap.add_argument("--encrypt", default="8,1", help="entries per call of the encrypt op, comma-separated")
     a = ap.parse_args()
     log_n, n = 16, 1 << 16
     bits = [51] + [46] * 16 + [51] * 14 + [51]
@@ -121,6 +185,12 @@ def main():
         q = qs[:limbs].view(*([1] * (len(shape) - 2)), limbs, 1)
         return torch.remainder(g, q)
 
+    st = torch.cuda.current_stream(eng.torch_device)
+    if a.ops == "encrypt":
+        # on its own: none of the key-switching keys the other ops need
+        for B in a.encrypt.split(","):
+            enc_bench(eng, rnd, L, n, int(B), a.prod_reps, a.rounds, st)
+        return
     eng.reserve(K - 1)
     keys = [rnd(L, 2, K, n, limbs=K) for _ in range(4)]
     for k in keys:
@@ -178,8 +248,11 @@ def main():
         "add": lambda: eng.add(cts[0], cts[1], rot_out[0]),
         "mulplain": lambda: eng.multiply_plain(cts[0], cts[2][0], rot_out[0]),
     }
-    st = torch.cuda.current_stream(eng.torch_device)
     names = a.ops.split(",")
+    if "encrypt" in names:
+        for B in a.encrypt.split(","):
+            enc_bench(eng, rnd, L, n, int(B), a.prod_reps, a.rounds, st)
+        names = [x for x in names if x != "encrypt"]
     if "prodseq" in names or "prodsum" in names:
         # both legs always run: their words are compared first, and the rounds interleave them
         for shape in a.prodsum.split(","):
