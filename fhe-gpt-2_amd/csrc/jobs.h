@@ -905,3 +905,96 @@ struct JobEncRow
         return v;
     }
 };
+
+// ------------------------------------------------------------- symmetric encryption of a batch
+// encrypt_zero_symmetric (keygen.h; rlwe.cpp:289-373) over primes 0 .. sample_limbs-1, stored limb k of
+// `stored` = keep + keep_last on prime k (k < keep) or on prime sample_limbs-1 (the last stored limb when
+// keep_last).  out is [2][stored][n]: c1 = a already holds the uniform sample, the error e is a byte
+// plane (sample.hip k_sk_cbd), and
+//     c0_k = -(a_k s_k + NTT_k(e)) (+ (q_{K-1} mod q_k) new_key_k on limb k = digit)      (mod q_k).
+__device__ __forceinline__ int sk_prime_of(int k, int keep, int sample_limbs)
+{
+    return k < keep ? k : sample_limbs - 1;
+}
+
+// Column pass: job k expands e to the prime of stored limb k (JobEncU's expansion) into scratch[k].
+struct JobSkE
+{
+    const u32 *e; // [n] bytes
+    u64 *scratch; // [stored][n]
+    const PrimeDev *primes;
+    const Tw *tw;
+    int keep, sample_limbs, log_n;
+    using View = JobEncU::View;
+    __device__ View view(int k) const
+    {
+        const int pi = sk_prime_of(k, keep, sample_limbs);
+        return View{ e, scratch + ((size_t)k << log_n), prime_at(primes, pi), tw + ((size_t)pi << log_n), false };
+    }
+};
+
+// Row pass: pre() forms g - a s with the pass's own loads (g the gadget term, 0 off limb `digit`), the
+// store subtracts the transform t of e and writes the canonical word: q - ((a s + t) mod q), 0 for 0,
+// plus g -- the words of mhe_multiply_plain, mhe_add, mhe_negate, mhe_multiply_scalar, mhe_add.
+struct JobSkRow
+{
+    u64 *scratch;       // [stored][n]
+    const u64 *sk;      // [K][n]
+    const u64 *new_key; // [K][n] or null
+    u64 *out;           // [2][stored][n]
+    const PrimeDev *primes;
+    const Tw *tw;
+    int keep, stored, sample_limbs, digit, K, log_n;
+    int fp = 0; // every prime < 2^51: the epilogue in exact FP64 (fparith.h)
+    struct View
+    {
+        u64 *buf;
+        const u64 *ap, *sp, *np;
+        u64 *outp;
+        PrimeDev p;
+        const Tw *tw;
+        u64 gad; // q_{K-1} mod q, canonical
+        bool skip, fp;
+        PrimeF f;
+        __device__ u64 load(u32 x) const { return buf[x]; }
+        // g - a s: a double's bits within 2.5q (FP) or the canonical residue
+        using Pre = u64;
+        __device__ Pre pre(u32 x) const
+        {
+            const u64 a = ap[x], s = sp[x], k = np ? np[x] : 0;
+            if (fp)
+            {
+                // canonical operands below 2^51: each product within 1.25q
+                const double g = np ? fp_mulmod_gen(fp_from_u52(k), fp_from_u52(gad), f.pd, f.pi) : 0.0;
+                return (u64)__double_as_longlong(g - fp_mulmod_gen(fp_from_u52(a), fp_from_u52(s), f.pd, f.pi));
+            }
+            const u64 g = np ? mulmod(k, gad, p) : 0;
+            return submod(g, mulmod(a, s, p), p.q);
+        }
+        __device__ void store(u32 x, u64 t, Pre o) const
+        {
+            if (fp) // t canonical: |g - a s - t| < 3.5q < 2^53, one canonicalisation
+                outp[x] = fp_canon(__longlong_as_double((long long)o) - fp_from_u52(t), f.pd, f.pi);
+            else // t in [0, 4q) -> canonical
+                outp[x] = submod(o, csub(csub(t, p.two_q), p.q), p.q);
+        }
+        __device__ void store(u32 x, u64 t) const { store(x, t, pre(x)); }
+    };
+    __device__ View view(int k) const
+    {
+        const int pi = sk_prime_of(k, keep, sample_limbs);
+        View v;
+        v.buf = scratch + ((size_t)k << log_n);
+        v.ap = out + ((size_t)(stored + k) << log_n);
+        v.sp = sk + ((size_t)pi << log_n);
+        v.np = (new_key && k == digit) ? new_key + ((size_t)pi << log_n) : nullptr;
+        v.outp = out + ((size_t)k << log_n);
+        v.p = prime_at(primes, pi);
+        v.tw = tw + ((size_t)pi << log_n);
+        v.gad = barrett64(prime_at(primes, K - 1).q, v.p);
+        v.skip = false;
+        v.fp = fp != 0;
+        v.f = prime_f(v.p);
+        return v;
+    }
+};

@@ -231,6 +231,7 @@ struct Workspace
     int *flags = nullptr;
     SumPool rotsum{ 4 };  // mhe_rotate_sum: A and T
     SumPool prodsum{ 6 }; // mhe_relin_sum_rescale: A, T and the sum C of the products' first two polys
+    Scratch sample;       // the on-device sample_poly_uniform's state, reject bit planes and redrawn words (sample.hip)
     // kernel timing (mhe_ctx_set_timing): event pairs recorded around the two dominant
     // key-switch kernels on this stream, read back by mhe_kernel_time
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[2];
@@ -243,6 +244,7 @@ struct Workspace
         hoist_base.release();
         rotsum.buf.release();
         prodsum.buf.release();
+        sample.release();
         if (flags) (void)hipFree(flags);
         flags = nullptr;
         for (auto &v : ev)
@@ -311,6 +313,10 @@ struct mhe_ctx
     std::atomic<unsigned long long> rotsum_sums{ 0 }, rotsum_terms{ 0 };             // mhe_rotsum_stats
     std::atomic<unsigned long long> prodsum_sums{ 0 }, prodsum_terms{ 0 };           // mhe_prodsum_stats
     std::atomic<unsigned long long> enc_entries{ 0 }, enc_groups{ 0 };               // mhe_encrypt_stats
+    std::atomic<unsigned long long> kg_entries{ 0 }, kg_groups{ 0 };                 // mhe_keygen_stats
+    std::atomic<unsigned> kg_cap_limit{ 0 }; // mhe_debug_keygen_cap: an upper limit on the redraw buffer's capacity (0: none)
+    unsigned long long id = 0;            // this context's number among all ever created (mhe_keygen_overflows)
+    unsigned long long *kg_dev = nullptr; // device totals: [0] redrawn uniform words, [1] overflowed entries (sample.hip)
     std::atomic<int> fail_alloc{ 0 }; // mhe_debug_fail_alloc: the n-th next allocation fails (0: off)
     TwF *cmodf = nullptr; // [K][K]: (q_j mod q_i, (q_j mod q_i) / q_i) as doubles, j major (hoist.h)
     std::mutex mask_mu;
@@ -774,6 +780,28 @@ int mhe_internal_primes(mhe_ctx *c, const PrimeDev **dev, const uint64_t **host,
     return MHE_OK;
 }
 
+// The sampling scratch of stream st with at least `bytes` bytes (grown here, before the caller's first
+// launch), and the context's device counters of the uniform sampler.
+int mhe_internal_sample_scratch(mhe_ctx *c, hipStream_t st, size_t bytes, void **scratch, uint64_t **counters)
+{
+    if (!valid_ctx(c) || !bytes) return fail(MHE_ERR_ARG, "invalid sampling arguments");
+    Workspace &w = ws_of(c, st);
+    std::lock_guard<std::mutex> g(w.mu);
+    if (w.sample.bytes < bytes)
+    {
+        int r = w.sample.grow(c, st, bytes);
+        if (r) return r;
+    }
+    *scratch = w.sample.p;
+    *counters = reinterpret_cast<uint64_t *>(c->kg_dev);
+    return MHE_OK;
+}
+
+uint32_t mhe_internal_keygen_cap_limit(mhe_ctx *c)
+{
+    return c->kg_cap_limit.load();
+}
+
 // ================================================================================ C ABI
 MHE_EXPORT const char *mhe_last_error(void)
 {
@@ -970,8 +998,11 @@ MHE_EXPORT int mhe_ctx_create(mhe_ctx **out, int log_n, const uint64_t *moduli, 
             c->nm_ks = m;
         }
     }
+    if (e == hipSuccess) e = hipMalloc(&c->kg_dev, 2 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(c->kg_dev, 0, 2 * sizeof(unsigned long long));
     if (e != hipSuccess)
     {
+        (void)hipFree(c->kg_dev);
         (void)hipFree(c->cmodf);
         (void)hipFree(c->twf);
         (void)hipFree(c->primes);
@@ -982,6 +1013,8 @@ MHE_EXPORT int mhe_ctx_create(mhe_ctx **out, int log_n, const uint64_t *moduli, 
         delete c;
         return fail(MHE_ERR_DEVICE, std::string("mhe_ctx_create: ") + hipGetErrorString(e));
     }
+    static std::atomic<unsigned long long> serial{ 0 };
+    c->id = ++serial;
     mhe_internal_ctx_count(+1);
     *out = c;
     return MHE_OK;
@@ -999,6 +1032,7 @@ MHE_EXPORT int mhe_ctx_destroy(mhe_ctx *c)
     (void)hipFree(c->invq);
     (void)hipFree(c->twf);
     (void)hipFree(c->cmodf);
+    (void)hipFree(c->kg_dev);
     delete c;
     mhe_internal_ctx_count(-1);
     return MHE_OK;
@@ -1750,6 +1784,9 @@ MHE_EXPORT int mhe_apply_galois_to(mhe_ctx *c, const uint64_t *in, uint64_t *out
 
 // ------------------------------------------------------- public-key encryption of a batch
 #include "encrypt.h"
+
+// ---------------------------------------- symmetric encryption of a batch: key-switching keys
+#include "keygen.h"
 
 MHE_EXPORT int mhe_rescale_batch(mhe_ctx *c, int count, const uint64_t *const *in, uint64_t *const *out, int size,
                                  int limbs, void *s)

@@ -10,6 +10,11 @@
 //     The GPU draws the bulk, reduces the accepted words of the limbs the caller keeps and lists
 //     the rejected indices (~q/2^64 of them); the host orders that list and assigns the
 //     replacement words from the stream tail (mhe_prng_apply_fixes writes them).
+//     mhe_prng_uniform_batch does all of it on the device for a batch of seeds (k_uni_bulk,
+//     k_uni_redraw below): the bulk marks its rejects in a bit plane, which keeps their order, and
+//     one workgroup per entry walks the tail limb by limb.  The redrawn words pass through a buffer
+//     whose capacity the host works out from the primes (sample_cap.h: mean + 12 standard
+//     deviations + 64 words).
 //   sample_poly_ternary (rlwe.cpp:21-38): one std::uniform_int_distribution<u64>(0, 2) draw per
 //     coefficient over a 32-bit adapter; libstdc++ 11 maps a 32-bit word g to (3g) >> 32
 //     (Lemire, bits/uniform_int_dist.h:246-270) and redraws only when g == 0 (probability 2^-32
@@ -25,9 +30,12 @@
 #include "../../include/mhe.h"
 #include "arith.h"
 #include "blake2b.h"
+#include "sample_cap.h"
 
 int mhe_internal_fail(int code, const char *msg);
 int mhe_internal_primes(mhe_ctx *c, const PrimeDev **dev, const uint64_t **host, int *count, int *log_n);
+int mhe_internal_sample_scratch(mhe_ctx *c, hipStream_t st, size_t bytes, void **scratch, uint64_t **counters);
+uint32_t mhe_internal_keygen_cap_limit(mhe_ctx *c);
 
 namespace
 {
@@ -318,19 +326,14 @@ __global__ void k_enc_ternary_fix(SeedB sb, signed char *small, size_t pitch, in
     state[2 * ent] = (u32)(pos - 4 * n);
 }
 
-// k_prng_cbd for error poly j = blockIdx.y of entry blockIdx.z, from byte 4n + 6n j + the entry's
-// extra bytes: a thread's 4 noise values leave as one dword.
-__global__ __launch_bounds__(256) void k_enc_cbd(SeedB sb, signed char *small, size_t pitch, int log_n, const u32 *state)
+// k_prng_cbd's noise values of coefficients [c0, c0 + cnt) (cnt <= kCbdCoeffs, a multiple of 4) from
+// the stream bytes at `start` on, one signed byte each: a thread's 4 values leave as one dword of o.
+__device__ __forceinline__ void cbd_bytes_wg(const Seed &s, u64 start, u64 cnt, u32 *o)
 {
     __shared__ u64 roots[kMaxRoots][8];
     __shared__ u64 bytes[kCbdBlocks * 8];
-    const int j = blockIdx.y, ent = blockIdx.z;
-    const u64 n = (u64)1 << log_n;
-    const u64 c0 = (u64)blockIdx.x * kCbdCoeffs;
-    const u64 cnt = (n - c0) < (u64)kCbdCoeffs ? (n - c0) : (u64)kCbdCoeffs; // a multiple of 4
-    const u64 start = 4 * n + 6 * n * (u64)j + state[2 * ent] + 6 * c0;
     const u64 b0 = start >> 6, b1 = (start + 6 * cnt - 1) >> 6;
-    load_roots(sb.s[ent], b0 >> 6, (int)((b1 >> 6) - (b0 >> 6) + 1), roots);
+    load_roots(s, b0 >> 6, (int)((b1 >> 6) - (b0 >> 6) + 1), roots);
     if (threadIdx.x <= b1 - b0)
     {
         u64 w[8];
@@ -354,8 +357,207 @@ __global__ __launch_bounds__(256) void k_enc_cbd(SeedB sb, signed char *small, s
                       __popc(byte_at(c + 3)) - __popc(byte_at(c + 4)) - __popc(byte_at(c + 5) & 0x1f);
         pk |= ((u32)v & 0xffu) << (8 * k);
     }
-    u32 *o = reinterpret_cast<u32 *>(small + (size_t)ent * pitch + (size_t)(1 + j) * n + c0);
     o[threadIdx.x] = pk;
+}
+
+// k_prng_cbd for error poly j = blockIdx.y of entry blockIdx.z, from byte 4n + 6n j + the entry's
+// extra bytes.
+__global__ __launch_bounds__(256) void k_enc_cbd(SeedB sb, signed char *small, size_t pitch, int log_n, const u32 *state)
+{
+    const int j = blockIdx.y, ent = blockIdx.z;
+    const u64 n = (u64)1 << log_n;
+    const u64 c0 = (u64)blockIdx.x * kCbdCoeffs;
+    const u64 cnt = (n - c0) < (u64)kCbdCoeffs ? (n - c0) : (u64)kCbdCoeffs; // a multiple of 4
+    const u64 start = 4 * n + 6 * n * (u64)j + state[2 * ent] + 6 * c0;
+    cbd_bytes_wg(sb.s[ent], start, cnt, reinterpret_cast<u32 *>(small + (size_t)ent * pitch + (size_t)(1 + j) * n + c0));
+}
+
+// The error of a symmetric encryption (encrypt_zero_symmetric, rlwe.cpp:289-373) of entry blockIdx.y:
+// CBD from stream byte 64 (the first 64 bytes seed the PRNG of a), plane small + entry * pitch.
+__global__ __launch_bounds__(256) void k_sk_cbd(SeedB sb, signed char *small, size_t pitch, int log_n)
+{
+    const int ent = blockIdx.y;
+    const u64 n = (u64)1 << log_n;
+    const u64 c0 = (u64)blockIdx.x * kCbdCoeffs;
+    const u64 cnt = (n - c0) < (u64)kCbdCoeffs ? (n - c0) : (u64)kCbdCoeffs;
+    cbd_bytes_wg(sb.s[ent], 64 + 6 * c0, cnt, reinterpret_cast<u32 *>(small + (size_t)ent * pitch + c0));
+}
+
+// ------------------------------------------------------ sample_poly_uniform, all on the device
+// For a batch of entries (seed, output) that share the limb maps.  state[entry][2] (zeroed before the
+// bulk): [0] nonzero when the bulk rejected a word, [1] nonzero when the redraw buffer overflowed.
+struct UniB
+{
+    Seed s[MHE_SAMPLE_MAXB];
+    u64 *out[MHE_SAMPLE_MAXB];
+};
+
+// k_prng_uniform for entry blockIdx.y.  Thread t of a workgroup owns words 8t .. 8t+7 of the
+// workgroup's 2048 (all in one limb: n >= 8) and leaves their reject bits as byte `blk` of the entry's
+// bit plane: bit g of the plane is word g of the stream, so the plane holds the rejects in stream order.
+__global__ __launch_bounds__(256) void k_uni_bulk(UniB ub, LimbMap map, const PrimeDev *primes, int limbs, int log_n,
+                                                  unsigned char *flags, size_t flag_pitch, u32 *state)
+{
+    __shared__ u64 roots[kMaxRoots][8];
+    const int ent = blockIdx.y;
+    const u64 b0 = (u64)blockIdx.x * 256, blk = b0 + threadIdx.x;
+    const u64 total = (u64)limbs << log_n;
+    const u64 last = ((total / 8 < b0 + 256) ? total / 8 : b0 + 256) - 1;
+    load_roots(ub.s[ent], b0 >> 6, (int)((last >> 6) - (b0 >> 6) + 1), roots);
+    if (blk * 8 >= total) return;
+    u64 w[8];
+    block_from_roots(roots, b0 >> 6, blk, w);
+    const int l = (int)((blk * 8) >> log_n);
+    const PrimeDev p = primes[map.prime[l]];
+    const u64 mm = ~0ULL - barrett64(~0ULL, p) - 1; // max_multiple (rlwe.cpp:152)
+    const int slot = map.slot[l];
+    u64 *o = ub.out[ent] + ((u64)(slot < 0 ? 0 : slot) << log_n) + ((blk * 8) & (((u64)1 << log_n) - 1));
+    u32 rej = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+    {
+        if (w[k] >= mm)
+            rej |= 1u << k;
+        else if (slot >= 0)
+            o[k] = barrett64(w[k], p);
+    }
+    flags[(size_t)ent * flag_pitch + blk] = (unsigned char)rej;
+    if (rej) state[2 * ent] = 1; // every writer stores the same word
+}
+
+// Exclusive prefix sum of v over the workgroup's 256 threads (thread order); total = the sum.
+__device__ __forceinline__ u32 wg_excl_scan(u32 v, u32 *sh, u32 &total)
+{
+    // four waves of 64 lanes (gfx950)
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    u32 x = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1)
+    {
+        const u32 y = __shfl_up(x, d);
+        if (lane >= d) x += y;
+    }
+    if (lane == 63) sh[wv] = x;
+    __syncthreads();
+    u32 off = 0, tot = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+    {
+        const u32 s = sh[i];
+        off += i < wv ? s : 0;
+        tot += s;
+    }
+    __syncthreads(); // sh is free again
+    total = tot;
+    return off + x - v;
+}
+
+// The redraws of sample_poly_uniform (rlwe.cpp:153-157) for entry blockIdx.x, one workgroup: returns
+// at once when the bulk rejected nothing (SEAL's own primes in practice).  The rejects are consumed in
+// stream order, so limb by limb, and max_multiple changes only between limbs.  Per limb:
+//   need   = the set bits of the limb's part of the bit plane;
+//   draw   the first `need` tail words below the limb's max_multiple, 2048 tail words per round (a
+//          thread per stream block, a workgroup scan for their ranks), into val[rank]; the tail
+//          position moves past the last word taken, so a word rejected here is skipped for good;
+//   apply  (kept limbs) the plane again, 2048 bits per round: the r-th set bit of the limb takes
+//          val[rank0 + r].
+// A rank at or beyond cap is neither written nor read: the entry's flag is raised and counted.
+// counters: [0] redrawn words, [1] overflowed entries (device totals, mhe_keygen_stats).
+__global__ __launch_bounds__(256) void k_uni_redraw(UniB ub, LimbMap map, const PrimeDev *primes, int limbs, int log_n,
+                                                    const unsigned char *flags, size_t flag_pitch, u64 *val,
+                                                    size_t val_pitch, u32 cap, u32 *state,
+                                                    unsigned long long *counters)
+{
+    const int ent = blockIdx.x, tid = threadIdx.x;
+    if (state[2 * ent] == 0) return; // uniform per workgroup
+    __shared__ u64 roots[kMaxRoots][8];
+    __shared__ u32 sh[4];
+    __shared__ u64 s_last;
+    const Seed &seed = ub.s[ent];
+    const unsigned char *fl = flags + (size_t)ent * flag_pitch;
+    u64 *vals = val + (size_t)ent * val_pitch;
+    const u32 n8 = 1u << (log_n - 3); // plane bytes per limb
+    u64 pos = (u64)limbs << log_n;    // next tail word
+    u32 rank0 = 0;
+    for (int l = 0; l < limbs; l++)
+    {
+        const unsigned char *fll = fl + (size_t)l * n8;
+        u32 c = 0, need;
+        for (u32 i = tid; i < n8; i += 256) c += __popc(fll[i]);
+        wg_excl_scan(c, sh, need);
+        if (need == 0) continue;
+        const PrimeDev p = primes[map.prime[l]];
+        const u64 mm = ~0ULL - barrett64(~0ULL, p) - 1;
+        u32 got = 0;
+        while (got < need)
+        {
+            // blocks b0 .. b0 + 255 span at most 5 buffers
+            const u64 b0 = pos >> 3, blk = b0 + tid;
+            load_roots(seed, b0 >> 6, (int)(((b0 + 255) >> 6) - (b0 >> 6) + 1), roots);
+            u64 w[8];
+            block_from_roots(roots, b0 >> 6, blk, w);
+            u32 ok = 0;
+#pragma unroll
+            for (int k = 0; k < 8; k++) ok |= (blk * 8 + k >= pos && w[k] < mm) ? 1u << k : 0;
+            u32 taken;
+            u32 a = got + wg_excl_scan(__popc(ok), sh, taken);
+#pragma unroll
+            for (int k = 0; k < 8; k++)
+                if ((ok >> k) & 1)
+                {
+                    if (a < need)
+                    {
+                        if (rank0 + a < cap) vals[rank0 + a] = barrett64(w[k], p);
+                        if (a == need - 1) s_last = blk * 8 + k;
+                    }
+                    a++;
+                }
+            __syncthreads(); // s_last, and the roots before the next round replaces them
+            if (got + taken >= need)
+            {
+                pos = s_last + 1;
+                got = need;
+            }
+            else
+            {
+                pos = (b0 + 256) << 3;
+                got += taken;
+            }
+            __syncthreads(); // s_last is read before a later round writes it
+        }
+        const int slot = map.slot[l];
+        if (slot >= 0)
+        {
+            // the barriers above order this workgroup's stores to vals before these loads
+            u64 *o = ub.out[ent] + ((u64)slot << log_n);
+            u32 base = rank0;
+            for (u32 c0 = 0; c0 < n8; c0 += 256)
+            {
+                const u32 i = c0 + tid;
+                const u32 f = i < n8 ? fll[i] : 0;
+                u32 cnt;
+                u32 r = base + wg_excl_scan(__popc(f), sh, cnt);
+#pragma unroll
+                for (int k = 0; k < 8; k++)
+                    if ((f >> k) & 1)
+                    {
+                        if (r < cap) o[(u64)i * 8 + k] = vals[r];
+                        r++;
+                    }
+                base += cnt;
+            }
+        }
+        rank0 += need;
+    }
+    if (tid == 0)
+    {
+        atomicAdd(&counters[0], (unsigned long long)rank0);
+        if (rank0 > cap)
+        {
+            state[2 * ent + 1] = 1;
+            atomicAdd(&counters[1], 1ull);
+        }
+    }
 }
 
 int launch_check(const char *what)
@@ -392,6 +594,131 @@ int mhe_internal_encrypt_samples(mhe_ctx *c, int B, const uint64_t (*seeds)[8], 
     hipLaunchKernelGGL(k_enc_cbd, dim3((unsigned)((n + kCbdCoeffs - 1) / kCbdCoeffs), 2, (unsigned)B), dim3(256), 0, st,
                        sb, small, pitch, log_n, (const u32 *)state);
     return launch_check("sampling kernel launch failed");
+}
+
+// Scratch of the on-device sample_poly_uniform for B entries: state [MHE_SAMPLE_MAXB][2] words, then
+// per entry a reject bit plane of limbs * n bits and `cap` redrawn words (sample_cap.h).
+namespace
+{
+struct UniLayout
+{
+    size_t flag_pitch, flags_at, val_at, bytes;
+    u32 cap;
+};
+UniLayout uni_layout(mhe_ctx *c, const uint64_t *q, int B, int limbs, const int *prime_of_limb, int log_n)
+{
+    UniLayout u;
+    u.cap = uniform_redraw_cap(q, prime_of_limb, limbs, (size_t)1 << log_n);
+    const u32 limit = mhe_internal_keygen_cap_limit(c); // mhe_debug_keygen_cap: the overflow side under test
+    if (limit && limit < u.cap) u.cap = limit;
+    u.flag_pitch = ((((size_t)limbs << log_n) / 8) + 255) & ~(size_t)255;
+    u.flags_at = 256;
+    u.val_at = u.flags_at + (size_t)B * u.flag_pitch;
+    u.bytes = u.val_at + (size_t)B * u.cap * sizeof(u64);
+    return u;
+}
+bool uni_maps_ok(int K, int log_n, int limbs, const int *prime_of_limb, const int *slot_of_limb)
+{
+    if (!prime_of_limb || !slot_of_limb || limbs < 1 || limbs > 64 || log_n < 5) return false;
+    for (int l = 0; l < limbs; l++)
+        if (prime_of_limb[l] < 0 || prime_of_limb[l] >= K || slot_of_limb[l] < -1 || slot_of_limb[l] > 63) return false;
+    return true;
+}
+} // namespace
+
+size_t mhe_internal_uniform_scratch_bytes(mhe_ctx *c, int B, int limbs, const int *prime_of_limb)
+{
+    const PrimeDev *primes;
+    const uint64_t *q;
+    int K, log_n;
+    if (mhe_internal_primes(c, &primes, &q, &K, &log_n)) return 0;
+    return uni_layout(c, q, B, limbs, prime_of_limb, log_n).bytes;
+}
+
+// sample_poly_uniform of B <= MHE_SAMPLE_MAXB entries into out[e] (the maps checked by the caller,
+// scratch of mhe_internal_uniform_scratch_bytes for at least B entries): the state reset and two launches.
+int mhe_internal_uniform_group(mhe_ctx *c, int B, const uint64_t (*seeds)[8], int limbs, const int *prime_of_limb,
+                               const int *slot_of_limb, uint64_t *const *out, void *scratch, uint64_t *counters,
+                               hipStream_t st)
+{
+    const PrimeDev *primes;
+    const uint64_t *q;
+    int K, log_n;
+    if (mhe_internal_primes(c, &primes, &q, &K, &log_n)) return mhe_internal_fail(MHE_ERR_ARG, "context is not valid");
+    if (B < 1 || B > MHE_SAMPLE_MAXB || !scratch || !counters)
+        return mhe_internal_fail(MHE_ERR_ARG, "invalid sampling arguments");
+    const UniLayout u = uni_layout(c, q, B, limbs, prime_of_limb, log_n);
+    UniB ub{};
+    LimbMap m;
+    for (int e = 0; e < B; e++)
+    {
+        for (int i = 0; i < 8; i++) ub.s[e].w[i] = seeds[e][i];
+        ub.out[e] = out[e];
+    }
+    for (int l = 0; l < 64; l++)
+    {
+        m.slot[l] = l < limbs ? (signed char)slot_of_limb[l] : -1;
+        m.prime[l] = l < limbs ? prime_of_limb[l] : 0;
+    }
+    u32 *state = static_cast<u32 *>(scratch);
+    unsigned char *flags = static_cast<unsigned char *>(scratch) + u.flags_at;
+    u64 *val = reinterpret_cast<u64 *>(static_cast<unsigned char *>(scratch) + u.val_at);
+    if (hipMemsetAsync(state, 0, 8 * (size_t)MHE_SAMPLE_MAXB, st) != hipSuccess)
+        return mhe_internal_fail(MHE_ERR_DEVICE, "sampling state reset failed");
+    const u64 blocks = ((u64)limbs << log_n) / 8;
+    hipLaunchKernelGGL(k_uni_bulk, dim3((unsigned)((blocks + 255) / 256), (unsigned)B), dim3(256), 0, st, ub, m, primes,
+                       limbs, log_n, flags, u.flag_pitch, state);
+    hipLaunchKernelGGL(k_uni_redraw, dim3((unsigned)B), dim3(256), 0, st, ub, m, primes, limbs, log_n,
+                       (const unsigned char *)flags, u.flag_pitch, val, (size_t)u.cap, u.cap, state,
+                       reinterpret_cast<unsigned long long *>(counters));
+    return launch_check("uniform sampling kernel launch failed");
+}
+
+// The error planes of B symmetric encryptions (keygen.h): small + e * pitch, n signed bytes each.
+int mhe_internal_sk_errors(mhe_ctx *c, int B, const uint64_t (*seeds)[8], signed char *small, size_t pitch, hipStream_t st)
+{
+    const PrimeDev *primes;
+    const uint64_t *q;
+    int K, log_n;
+    if (mhe_internal_primes(c, &primes, &q, &K, &log_n)) return mhe_internal_fail(MHE_ERR_ARG, "context is not valid");
+    if (!seeds || !small || B < 1 || B > MHE_SAMPLE_MAXB || log_n < 5 || (((uintptr_t)small | pitch) & 3) ||
+        (B > 1 && pitch < ((size_t)1 << log_n)))
+        return mhe_internal_fail(MHE_ERR_ARG, "invalid sampling arguments");
+    SeedB sb{};
+    for (int e = 0; e < B; e++)
+        for (int i = 0; i < 8; i++) sb.s[e].w[i] = seeds[e][i];
+    const u64 n = (u64)1 << log_n;
+    hipLaunchKernelGGL(k_sk_cbd, dim3((unsigned)((n + kCbdCoeffs - 1) / kCbdCoeffs), (unsigned)B), dim3(256), 0, st, sb,
+                       small, pitch, log_n);
+    return launch_check("sampling kernel launch failed");
+}
+
+MHE_EXPORT int mhe_prng_uniform_batch(mhe_ctx *c, int count, const uint64_t (*seeds)[8], int limbs,
+                                      const int *prime_of_limb, const int *slot_of_limb, uint64_t *const *out,
+                                      void *stream)
+{
+    const PrimeDev *primes;
+    const uint64_t *q;
+    int K, log_n;
+    if (mhe_internal_primes(c, &primes, &q, &K, &log_n)) return mhe_internal_fail(MHE_ERR_ARG, "context is not valid");
+    if (count < 1 || !seeds || !out || !uni_maps_ok(K, log_n, limbs, prime_of_limb, slot_of_limb))
+        return mhe_internal_fail(MHE_ERR_ARG, "invalid sampling arguments");
+    for (int i = 0; i < count; i++)
+        if (!out[i]) return mhe_internal_fail(MHE_ERR_ARG, "invalid sampling arguments");
+    hipStream_t st = (hipStream_t)stream;
+    const int Bmax = count < MHE_SAMPLE_MAXB ? count : MHE_SAMPLE_MAXB;
+    void *scratch;
+    uint64_t *counters;
+    int r = mhe_internal_sample_scratch(c, st, uni_layout(c, q, Bmax, limbs, prime_of_limb, log_n).bytes, &scratch, &counters);
+    if (r) return r;
+    for (int b0 = 0; b0 < count; b0 += MHE_SAMPLE_MAXB)
+    {
+        const int B = count - b0 < MHE_SAMPLE_MAXB ? count - b0 : MHE_SAMPLE_MAXB;
+        if ((r = mhe_internal_uniform_group(c, B, seeds + b0, limbs, prime_of_limb, slot_of_limb, out + b0, scratch,
+                                            counters, st)))
+            return r;
+    }
+    return MHE_OK;
 }
 
 MHE_EXPORT int mhe_prng_uniform_bulk(mhe_ctx *c, const uint64_t seed[8], int limbs, const int *prime_of_limb,

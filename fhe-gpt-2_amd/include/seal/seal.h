@@ -647,8 +647,19 @@ public:
 
 private:
     // seeds (optional) receives each digit's public seed (the PRNG seed of its c1)
+    // drawn (optional) receives the digits' bootstrap seeds when the key came from one batched launch
+    // sequence (mhe_encrypt_sk_batch); it stays empty when the per-digit sequence ran
     void kswitch_key(const std::uint64_t *new_key_dev, PolyStore &dest, std::size_t digits,
-                     std::vector<prng_seed_type> *seeds = nullptr);
+                     std::vector<prng_seed_type> *seeds = nullptr, std::vector<prng_seed_type> *drawn = nullptr);
+    // a key made by the batched path: enough to make it again from its seeds
+    struct MadeKey
+    {
+        std::size_t index;
+        std::uint32_t elt; // 0: the relinearization key
+        std::size_t digits;
+        std::vector<prng_seed_type> seeds;
+    };
+    void redo_if_overflowed(KSwitchKeys &destination, const std::vector<MadeKey> &made);
     void relin_keys_into(RelinKeys &destination, SeedMap *seeds);
     void galois_keys_into(const std::vector<std::uint32_t> &elts, GaloisKeys &destination, SeedMap *seeds);
     SEALContext ctx_;

@@ -124,6 +124,12 @@ SIGNATURES = {
     "mhe_encrypt_pk_batch": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp, ctypes.c_int, vp]),
     "mhe_encrypt_stats": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
                                          ctypes.c_int]),
+    "mhe_prng_uniform_batch": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, vp, vp]),
+    "mhe_encrypt_sk_batch": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp,
+                                            vp, vp, vp]),
+    "mhe_keygen_stats": (ctypes.c_int, [vp] + [ctypes.POINTER(ctypes.c_uint64)] * 4 + [ctypes.c_int]),
+    "mhe_keygen_overflows": (ctypes.c_int, [vp, vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "mhe_debug_keygen_cap": (ctypes.c_int, [vp, ctypes.c_uint32]),
 }
 
 
@@ -554,6 +560,45 @@ class Engine:
         e, g = ctypes.c_uint64(), ctypes.c_uint64()
         _check(lib().mhe_encrypt_stats(self._h, ctypes.byref(e), ctypes.byref(g), 1 if reset else 0))
         return e.value, g.value
+
+    def prng_uniform_batch(self, seeds, limbs, outs=None, prime_of_limb=None, slot_of_limb=None):
+        """mhe_prng_uniform_batch: outs[i][slot][n] = sample_poly_uniform(Blake2xbPRNG(seeds[i])) over
+        `limbs` limbs (limb l on prime prime_of_limb[l], default l, kept in slot slot_of_limb[l], default
+        l, -1: dropped), the rejected words redrawn in stream order on the device."""
+        cnt = len(seeds)
+        sd = np.ascontiguousarray(np.array(seeds, np.uint64).reshape(cnt, 8))
+        pr = np.ascontiguousarray(np.arange(limbs) if prime_of_limb is None else prime_of_limb, dtype=np.int32)
+        sl = np.ascontiguousarray(np.arange(limbs) if slot_of_limb is None else slot_of_limb, dtype=np.int32)
+        outs = [self.empty(int(sl.max()) + 1, self.n) for _ in range(cnt)] if outs is None else outs
+        _check(lib().mhe_prng_uniform_batch(self._h, cnt, sd.ctypes.data_as(ctypes.c_void_p), limbs,
+                                            pr.ctypes.data_as(ctypes.c_void_p), sl.ctypes.data_as(ctypes.c_void_p),
+                                            self._ptrs(outs), self.stream()))
+        return outs
+
+    def encrypt_sk_batch(self, seeds, sk, sample_limbs, keep, keep_last, new_keys=None, digits=None, outs=None):
+        """mhe_encrypt_sk_batch: outs[i] [2][keep + keep_last][n] = encrypt_zero_symmetric drawn from
+        Blake2xbPRNG(seeds[i]) under sk [K][n] over primes 0..sample_limbs-1, restricted to limbs
+        0..keep-1 (and the last one with keep_last), plus the gadget term of new_keys[i] [K][n] on limb
+        digits[i] of c0 where it is not None -- one launch sequence per 8 entries."""
+        cnt = len(seeds)
+        sd = np.ascontiguousarray(np.array(seeds, np.uint64).reshape(cnt, 8))
+        outs = [self.empty(2, keep + keep_last, self.n) for _ in range(cnt)] if outs is None else outs
+        nk = None if new_keys is None else (ctypes.c_void_p * cnt)(*[None if k is None else k.data_ptr() for k in new_keys])
+        dg = None if digits is None else (ctypes.c_int * cnt)(*[int(d) for d in digits])
+        _check(lib().mhe_encrypt_sk_batch(self._h, cnt, sd.ctypes.data_as(ctypes.c_void_p), _ptr(sk), sample_limbs, keep,
+                                          keep_last, nk, dg, self._ptrs(outs), self.stream()))
+        return outs
+
+    def keygen_stats(self, reset=False):
+        """mhe_keygen_stats: (entries, launch groups) of encrypt_sk_batch and the uniform sampler's
+        device totals (redrawn words, overflowed entries); waits for the device."""
+        v = [ctypes.c_uint64() for _ in range(4)]
+        _check(lib().mhe_keygen_stats(self._h, *[ctypes.byref(x) for x in v], 1 if reset else 0))
+        return tuple(x.value for x in v)
+
+    def debug_keygen_cap(self, cap):
+        """mhe_debug_keygen_cap: limit the uniform sampler's redraw buffer to `cap` words (0: no limit)."""
+        _check(lib().mhe_debug_keygen_cap(self._h, int(cap)))
 
     def rescale_batch(self, cts, outs=None):
         size, L = cts[0].shape[0], cts[0].shape[1]

@@ -44,9 +44,12 @@ namespace
 // encryption of zero over the key level (its own bootstrap seed, next_seed()) with
 // (P mod q_j) * new_key added to limb j of c0; the stored key keeps primes q_0..q_{digits-1} and
 // P ([digits][2][digits+1][n]).  digits = K-1 is SEAL's full key; a truncated key is SEAL's key
-// restricted to those digits and primes (the whole digit is drawn, then the kept limbs copied).
-void make_kswitch_key(const SEALContext &ctx, const std::function<prng_seed_type()> &next_seed,
-                      const std::uint64_t *sk, const std::uint64_t *new_key, std::size_t digits, PolyStore &dest)
+// restricted to those digits and primes.
+// The per-digit sequence of general-purpose calls (the whole digit is drawn over the key level, then
+// the kept limbs copied): the path with batched launches off, and the redo of a key whose uniform
+// sampler overflowed its redraw buffer.
+void make_kswitch_key_seq(const SEALContext &ctx, const std::function<prng_seed_type()> &next_seed,
+                          const std::uint64_t *sk, const std::uint64_t *new_key, std::size_t digits, PolyStore &dest)
 {
     const std::size_t K = ctx.key_size(), n = ctx.key_context_data()->parms().poly_modulus_degree();
     const auto &cm = ctx.key_context_data()->parms().coeff_modulus();
@@ -79,6 +82,52 @@ void make_kswitch_key(const SEALContext &ctx, const std::function<prng_seed_type
                 chk(mhe_memcpy_d2d(eng, dst + digits * n, src + (K - 1) * n, n * 8, s));
             }
     }
+}
+
+// The same key from one mhe_encrypt_sk_batch over all digits, written straight into the destination
+// store: the seeds are drawn in digit order on the host, nothing synchronises.  `drawn` receives the
+// bootstrap seeds, with which a caller redoes the key by make_kswitch_key_seq when the engine reports
+// an overflow at the end of its create_* call (redo_if_overflowed).
+void make_kswitch_key(const SEALContext &ctx, const std::function<prng_seed_type()> &next_seed,
+                      const std::uint64_t *sk, const std::uint64_t *new_key, std::size_t digits, PolyStore &dest,
+                      std::vector<prng_seed_type> *drawn = nullptr)
+{
+    if (!batched_launches() || trace::enabled()) return make_kswitch_key_seq(ctx, next_seed, sk, new_key, digits, dest);
+    const std::size_t K = ctx.key_size(), n = ctx.key_context_data()->parms().poly_modulus_degree();
+    if (K < 2) throw std::logic_error("keyswitching is not supported by the context");
+    if (digits < 1 || digits > K - 1) throw std::invalid_argument("key digits out of range");
+    void *s = ctx.stream();
+    const std::size_t KL = digits + 1; // stored limbs
+    dest.bind(ctx);
+    dest.resize_words(digits * 2 * KL * n, false);
+    std::uint64_t *d = dest.dev_write(s, true);
+    std::vector<prng_seed_type> seeds(digits);
+    std::vector<const std::uint64_t *> nk(digits, new_key);
+    std::vector<int> dg(digits);
+    std::vector<std::uint64_t *> outs(digits);
+    for (std::size_t j = 0; j < digits; j++)
+    {
+        seeds[j] = next_seed();
+        dg[j] = (int)j;
+        outs[j] = d + j * 2 * KL * n;
+    }
+    chk(mhe_encrypt_sk_batch(ctx.engine(), (int)digits, reinterpret_cast<const std::uint64_t(*)[8]>(seeds.data()), sk,
+                             (int)K, (int)digits, 1, nk.data(), dg.data(), outs.data(), s));
+    if (drawn) *drawn = std::move(seeds);
+}
+
+// A function that hands out `seeds` in order (the replay of a key's draws).
+std::function<prng_seed_type()> replay(const std::vector<prng_seed_type> &seeds)
+{
+    auto i = std::make_shared<std::size_t>(0);
+    return [&seeds, i] { return seeds.at((*i)++); };
+}
+
+// The one synchronisation of a create_* call that took the batched path: true when a key it made may
+// hold words of an overflowed redraw buffer and has to be redone.
+bool overflowed(const SEALContext &ctx)
+{
+    return batched_launches() && !trace::enabled() && rnd::uniform_overflow_moved(ctx.engine(), ctx.stream());
 }
 } // namespace
 
@@ -150,6 +199,7 @@ const std::uint64_t *KSwitchKeys::key_for(std::size_t i, std::size_t L, void *st
                 chk(mhe_permute_galois(ctx.engine(), sk, e->second.first, rot.p, 1, (int)K, s));
                 Blake2xbPRNG seeds(e->second.second);
                 PolyStore fresh;
+                std::vector<prng_seed_type> drawn;
                 make_kswitch_key(
                     ctx,
                     [&] {
@@ -157,7 +207,8 @@ const std::uint64_t *KSwitchKeys::key_for(std::size_t i, std::size_t L, void *st
                         seeds.generate(prng_seed_byte_count, reinterpret_cast<seal_byte *>(d.data()));
                         return d;
                     },
-                    sk, rot.p, digits, fresh);
+                    sk, rot.p, digits, fresh, &drawn);
+                if (!drawn.empty() && overflowed(ctx)) make_kswitch_key_seq(ctx, replay(drawn), sk, rot.p, digits, fresh);
                 auto kt = keys_.find(i);
                 if (kt != keys_.end()) retired_.push_back(std::move(kt->second));
                 keys_[i] = std::move(fresh);
@@ -242,7 +293,16 @@ prng_seed_type make_public_key(const SEALContext &ctx, UniformRandomGeneratorFac
     pk.scale() = 1.0;
     std::uint64_t *d = pk.store().dev_write(s, true);
     const prng_seed_type seed = rng.next_seed();
-    sym_encrypt_zero(ctx, seed, sk.data().store().dev_read(s), K, d, d + K * n, s);
+    const std::uint64_t *skp = sk.data().store().dev_read(s);
+    bool batched = batched_launches() && !trace::enabled();
+    if (batched)
+    {
+        // one entry, every limb of the key level kept: [2][K][n] is the public key's own layout
+        chk(mhe_encrypt_sk_batch(ctx.engine(), 1, reinterpret_cast<const std::uint64_t(*)[8]>(seed.data()), skp, (int)K,
+                                 (int)K, 0, nullptr, nullptr, &d, s));
+        batched = !overflowed(ctx);
+    }
+    if (!batched) sym_encrypt_zero(ctx, seed, skp, K, d, d + K * n, s);
     return rnd::stream_prefix_seed(seed);
 }
 } // namespace
@@ -257,7 +317,7 @@ Serializable<PublicKey> KeyGenerator::create_public_key()
 }
 
 void KeyGenerator::kswitch_key(const std::uint64_t *new_key, PolyStore &dest, std::size_t digits,
-                               std::vector<prng_seed_type> *seeds)
+                               std::vector<prng_seed_type> *seeds, std::vector<prng_seed_type> *drawn)
 {
     make_kswitch_key(
         ctx_,
@@ -266,7 +326,29 @@ void KeyGenerator::kswitch_key(const std::uint64_t *new_key, PolyStore &dest, st
             if (seeds) seeds->push_back(rnd::stream_prefix_seed(sd));
             return sd;
         },
-        sk_.data().store().dev_read(ctx_.stream()), new_key, digits, dest);
+        sk_.data().store().dev_read(ctx_.stream()), new_key, digits, dest, drawn);
+}
+
+// The end of a create_* call: when the engine reports an overflowed redraw buffer, every key the call
+// made (index, Galois element or 0 for the relinearization key, digits, bootstrap seeds) is made again
+// from its seeds by the per-digit sequence and replaces the batched one.
+void KeyGenerator::redo_if_overflowed(KSwitchKeys &destination, const std::vector<MadeKey> &made)
+{
+    if (made.empty() || !overflowed(ctx_)) return;
+    const std::size_t K = ctx_.key_size(), n = ctx_.key_context_data()->parms().poly_modulus_degree();
+    void *s = ctx_.stream();
+    DevBuf nk(ctx_.engine(), s, K * n);
+    const std::uint64_t *sk = sk_.data().store().dev_read(s);
+    for (const MadeKey &m : made)
+    {
+        if (m.elt)
+            chk(mhe_permute_galois(ctx_.engine(), sk, m.elt, nk.p, 1, (int)K, s));
+        else
+            chk(mhe_multiply_plain(ctx_.engine(), sk, sk, nk.p, 1, (int)K, s));
+        PolyStore key;
+        make_kswitch_key_seq(ctx_, replay(m.seeds), sk, nk.p, m.digits, key);
+        destination.insert(m.index, std::move(key), m.digits + 1);
+    }
 }
 
 void KeyGenerator::create_relin_keys(RelinKeys &destination) { relin_keys_into(destination, nullptr); }
@@ -288,8 +370,11 @@ void KeyGenerator::relin_keys_into(RelinKeys &destination, SeedMap *seeds)
     const std::uint64_t *sk = sk_.data().store().dev_read(s);
     chk(mhe_multiply_plain(ctx_.engine(), sk, sk, s2.p, 1, (int)K, s));
     PolyStore key;
-    kswitch_key(s2.p, key, K - 1, seeds ? &(*seeds)[RelinKeys::get_index(2)] : nullptr);
+    std::vector<MadeKey> made(1, MadeKey{ RelinKeys::get_index(2), 0, K - 1, {} });
+    kswitch_key(s2.p, key, K - 1, seeds ? &(*seeds)[RelinKeys::get_index(2)] : nullptr, &made[0].seeds);
     destination.insert(RelinKeys::get_index(2), std::move(key), K);
+    if (made[0].seeds.empty()) made.clear(); // the per-digit sequence ran
+    redo_if_overflowed(destination, made);
     destination.parms_id() = ctx_.key_parms_id();
     destination.set_key_limbs(K);
 }
@@ -304,6 +389,7 @@ void KeyGenerator::create_galois_keys(const std::vector<std::pair<std::uint32_t,
     if (K < 2) throw std::logic_error("keyswitching is not supported by the context");
     void *s = ctx_.stream();
     DevBuf rot(ctx_.engine(), s, K * n);
+    std::vector<MadeKey> made;
     for (const auto &el : elt_limbs)
     {
         const std::uint32_t elt = el.first;
@@ -313,9 +399,12 @@ void KeyGenerator::create_galois_keys(const std::vector<std::pair<std::uint32_t,
         const std::uint64_t *sk = sk_.data().store().dev_read(s);
         chk(mhe_permute_galois(ctx_.engine(), sk, elt, rot.p, 1, (int)K, s));
         PolyStore key;
-        kswitch_key(rot.p, key, digits);
-        destination.insert(GaloisKeys::get_index(elt), std::move(key), digits + 1);
+        MadeKey m{ GaloisKeys::get_index(elt), elt, digits, {} };
+        kswitch_key(rot.p, key, digits, nullptr, &m.seeds);
+        destination.insert(m.index, std::move(key), digits + 1);
+        if (!m.seeds.empty()) made.push_back(std::move(m));
     }
+    redo_if_overflowed(destination, made);
     destination.parms_id() = ctx_.key_parms_id();
     destination.set_key_limbs(K);
 }
@@ -333,6 +422,7 @@ void KeyGenerator::galois_keys_into(const std::vector<std::uint32_t> &elts, Galo
     if (K < 2) throw std::logic_error("keyswitching is not supported by the context");
     void *s = ctx_.stream();
     DevBuf rot(ctx_.engine(), s, K * n);
+    std::vector<MadeKey> made;
     for (std::uint32_t elt : elts)
     {
         if (!(elt & 1) || elt >= 2 * n) throw std::invalid_argument("Galois element is not valid");
@@ -340,9 +430,12 @@ void KeyGenerator::galois_keys_into(const std::vector<std::uint32_t> &elts, Galo
         const std::uint64_t *sk = sk_.data().store().dev_read(s);
         chk(mhe_permute_galois(ctx_.engine(), sk, elt, rot.p, 1, (int)K, s));
         PolyStore key;
-        kswitch_key(rot.p, key, K - 1, seeds ? &(*seeds)[GaloisKeys::get_index(elt)] : nullptr);
-        destination.insert(GaloisKeys::get_index(elt), std::move(key), K);
+        MadeKey m{ GaloisKeys::get_index(elt), elt, K - 1, {} };
+        kswitch_key(rot.p, key, K - 1, seeds ? &(*seeds)[m.index] : nullptr, &m.seeds);
+        destination.insert(m.index, std::move(key), K);
+        if (!m.seeds.empty()) made.push_back(std::move(m));
     }
+    redo_if_overflowed(destination, made);
     destination.parms_id() = ctx_.key_parms_id();
     destination.set_key_limbs(K);
 }

@@ -1,8 +1,9 @@
 // random.cpp -- SEAL's randomness for the seal:: surface: OS entropy, Blake2xbPRNG and its
 // factory (SEAL/randomgen.h:200-560, randomgen.cpp:23-195), and the samplers of
 // SEAL/util/rlwe.cpp driven on the device (csrc/sample.hip) with the host doing only what is
-// sequential: the sparse ternary secret key (rlwe.cpp:40-70) and the ordering of the few
-// rejected uniform words (rlwe.cpp:148-160).
+// sequential: the sparse ternary secret key (rlwe.cpp:40-70).  The rejected uniform words
+// (rlwe.cpp:148-160) are ordered and redrawn on the device; the host walk that did it before is the
+// path with batched launches off and the redo after an overflowed redraw buffer.
 #include "random_internal.h"
 
 #include "../../include/mhe.h"
@@ -12,6 +13,7 @@
 #include <cerrno>
 #include <cstring>
 #include <fstream>
+#include <map>
 #include <stdexcept>
 #include <sys/random.h>
 
@@ -168,9 +170,34 @@ struct Scratch
 };
 } // namespace
 
+bool uniform_overflow_moved(mhe_ctx *eng, void *s)
+{
+    // keyed by the engine's creation number, which no later engine shares (its address may be reused)
+    thread_local std::map<std::uint64_t, std::uint64_t> seen;
+    std::uint64_t now = 0, id = 0;
+    check(mhe_keygen_overflows(eng, s, &now, &id));
+    std::uint64_t &last = seen[id]; // a new engine starts at 0, as a fresh map entry does
+    const bool moved = now != last;
+    last = now;
+    return moved;
+}
+
 void sample_uniform_dev(mhe_ctx *eng, const prng_seed_type &seed, const std::vector<std::uint64_t> &moduli,
                         const std::vector<int> &prime_of_limb, const std::vector<int> &slot_of_limb, std::size_t n,
                         std::uint64_t *out, void *s)
+{
+    if (batched_launches())
+    {
+        check(mhe_prng_uniform_batch(eng, 1, reinterpret_cast<const std::uint64_t(*)[8]>(seed.data()),
+                                     (int)prime_of_limb.size(), prime_of_limb.data(), slot_of_limb.data(), &out, s));
+        if (!uniform_overflow_moved(eng, s)) return;
+    }
+    sample_uniform_host_walk(eng, seed, moduli, prime_of_limb, slot_of_limb, n, out, s);
+}
+
+void sample_uniform_host_walk(mhe_ctx *eng, const prng_seed_type &seed, const std::vector<std::uint64_t> &moduli,
+                              const std::vector<int> &prime_of_limb, const std::vector<int> &slot_of_limb,
+                              std::size_t n, std::uint64_t *out, void *s)
 {
     const std::size_t limbs = prime_of_limb.size();
     constexpr std::uint32_t cap = 1u << 16;

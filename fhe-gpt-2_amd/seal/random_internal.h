@@ -15,10 +15,21 @@ prng_seed_type stream_prefix_seed(const prng_seed_type &seed);
 
 // sample_poly_uniform(Blake2xbPRNG(seed)) over limbs 0..L-1 (limb l reduced mod
 // moduli[prime_of_limb[l]]); limbs with slot_of_limb[l] >= 0 are written to out[slot][n] on the
-// device.  Synchronises stream s (the rejected words are ordered on the host).
+// device.  With batched launches on (seal::set_batched_launches) this is one mhe_prng_uniform_batch -- the
+// rejected words are ordered and redrawn on the device -- and one synchronisation of stream s to learn
+// whether its redraw buffer overflowed (then, and with batched launches off, sample_uniform_host_walk).
 void sample_uniform_dev(mhe_ctx *eng, const prng_seed_type &seed, const std::vector<std::uint64_t> &moduli,
                         const std::vector<int> &prime_of_limb, const std::vector<int> &slot_of_limb, std::size_t n,
                         std::uint64_t *out, void *s);
+// The same words with the rejected indices downloaded, ordered on the host and redrawn by a host walk
+// of the stream tail (up to 65536 rejects): one to three synchronisations of stream s.
+void sample_uniform_host_walk(mhe_ctx *eng, const prng_seed_type &seed, const std::vector<std::uint64_t> &moduli,
+                              const std::vector<int> &prime_of_limb, const std::vector<int> &slot_of_limb,
+                              std::size_t n, std::uint64_t *out, void *s);
+// Waits for stream s; true when the engine's count of overflowed redraw buffers (mhe_keygen_overflows)
+// is not the one this thread saw at its last call for this engine.  Never misses an overflow of the
+// calling thread's own work on s; another thread's overflow can make it true as well.
+bool uniform_overflow_moved(mhe_ctx *eng, void *s);
 // ... over limbs 0..limbs-1 of the context, all kept
 void sample_uniform_dev(mhe_ctx *eng, const prng_seed_type &seed, const std::vector<std::uint64_t> &moduli,
                         std::size_t limbs, std::size_t n, std::uint64_t *out, void *s);

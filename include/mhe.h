@@ -488,6 +488,59 @@ int mhe_encrypt_pk_batch(mhe_ctx *ctx, int count, const uint64_t (*seeds)[8], co
                          const uint64_t *const *plain, uint64_t *const *out, int limbs, void *stream);
 int mhe_encrypt_stats(mhe_ctx *ctx, uint64_t *entries, uint64_t *launch_groups, int reset);
 
+/* sample_poly_uniform (rlwe.cpp:136-162) entirely on the device, for a batch of seeds that share the
+ * limb maps (their meaning as in mhe_prng_uniform_bulk): out[i][slot][n] receives
+ * sample_poly_uniform(Blake2xbPRNG(seeds[i])) over limbs 0..limbs-1, that is the bulk words with every
+ * word >= max_multiple redrawn in stream-index order from the words after the bulk; a tail word that
+ * is itself rejected for the consuming index's prime is skipped.  A limb with slot_of_limb[l] < 0 is
+ * not written, but its rejects still consume tail words.  Up to 8 entries per launch sequence (the
+ * state reset, the bulk, the redraw: the bulk marks its rejects in a bit plane, one workgroup per
+ * entry walks the tail limb by limb and returns at once when nothing was rejected), more in groups.
+ * Stream-ordered: no host synchronisation, no download, no host-side sort or tail walk.
+ * The redrawn words pass through a per-entry buffer in the stream's scratch, grown before the first
+ * launch and sized on the host from the primes: with p_l = ((2^64 - 1) mod q_l + 2) / 2^64 the reject
+ * probability of a word of limb l,
+ *     capacity = ceil(sum_l n p_l + 12 sqrt(sum_l n p_l (1 - p_l))) + 64 words
+ * (csrc/sample_cap.h).  A draw with more rejects writes nothing out of bounds: the words beyond the
+ * capacity keep their rejected bulk slots unwritten, the entry's device flag is raised and
+ * mhe_keygen_stats counts it in `overflows`. */
+int mhe_prng_uniform_batch(mhe_ctx *ctx, int count, const uint64_t (*seeds)[8], int limbs, const int *prime_of_limb,
+                           const int *slot_of_limb, uint64_t *const *out, void *stream);
+/* Symmetric encryption of a batch: out[i] is [2][stored][n], stored = keep + keep_last, c0 then c1 --
+ * the stored layout of one key-switching key digit, of a public key or of a ciphertext -- and holds
+ * encrypt_zero_symmetric (rlwe.cpp:289-373) drawn from Blake2xbPRNG(seeds[i]) over primes
+ * 0..sample_limbs-1: c1 = a uniform from the PRNG seeded with the stream's first 64 bytes, e CBD from
+ * byte 64 of the same stream, c0 = -(a s + NTT(e)), both restricted to limbs 0..keep-1 plus limb
+ * sample_limbs-1 when keep_last is set.  sk is [K][n] at the key level, NTT form.  When new_key[i] is
+ * not NULL ([K][n], key level), (q_{K-1} mod q_j) new_key[i][j] is added to limb j = digit[i] of c0
+ * (generate_one_kswitch_key, keygenerator.cpp:384-414); new_key may be NULL: no entry has one.
+ * Word for word the sequence mhe_prng_uniform_bulk (+ fixes), mhe_prng_small, mhe_ntt_forward,
+ * mhe_multiply_plain, mhe_add, mhe_negate, mhe_multiply_scalar, mhe_add, and the copies of the kept
+ * limbs.  Launches per group of up to 8 entries: the state reset, the two kernels of
+ * mhe_prng_uniform_batch writing a into c1's kept slots, the error as one signed byte per
+ * coefficient, and one forward NTT of the kept limbs whose row pass forms c0.
+ * 1 <= sample_limbs <= K; keep >= 0, keep + keep_last >= 1, keep <= sample_limbs - keep_last;
+ * keep_last or a new key require sample_limbs == K; 0 <= digit[i] < keep; count >= 1; outputs
+ * disjoint from each other, from sk and from every new key.  All arguments are checked and all scratch
+ * is grown before the first launch: a failed call leaves every out[i] as it was.  Stream-ordered, no
+ * host synchronisation.  mhe_op_counts sees the sequence's op mix at sample_limbs limbs: per entry one
+ * NTT, one plaintext product and two additions, plus one scalar product and one addition for a new key.
+ * mhe_keygen_stats: entries and launch groups of mhe_encrypt_sk_batch, and the device totals of the
+ * uniform sampler (both entry points): words redrawn, entries whose redraw buffer overflowed.  It
+ * waits for the device.  mhe_keygen_overflows: the overflow total after waiting for `stream` only, and
+ * the context's number among all contexts ever created, which no later context shares (a key generator
+ * compares the total with the one it saw last for that number and, when it moved, redoes every key of
+ * its create call: the per-entry device flag lives only until the next launch group's reset).
+ * mhe_debug_keygen_cap: an upper limit on the redraw buffer's capacity in words (0: none), for tests of
+ * the overflow side in the style of mhe_debug_fail_alloc. */
+int mhe_encrypt_sk_batch(mhe_ctx *ctx, int count, const uint64_t (*seeds)[8], const uint64_t *sk, int sample_limbs,
+                         int keep, int keep_last, const uint64_t *const *new_key, const int *digit,
+                         uint64_t *const *out, void *stream);
+int mhe_keygen_stats(mhe_ctx *ctx, uint64_t *entries, uint64_t *launch_groups, uint64_t *redrawn_words,
+                     uint64_t *overflows, int reset);
+int mhe_keygen_overflows(mhe_ctx *ctx, void *stream, uint64_t *overflows, uint64_t *ctx_id);
+int mhe_debug_keygen_cap(mhe_ctx *ctx, uint32_t cap);
+
 #ifdef __cplusplus
 }
 #endif

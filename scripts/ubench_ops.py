@@ -13,6 +13,14 @@ encseqB / encbatchB (--ops encrypt --encrypt B,...): B public-key encryptions wi
 the sequence of Encryptor::encrypt (3 mhe_prng_small, 2 mhe_ntt_forward, 2 x (mhe_multiply_plain, mhe_add),
 mhe_rescale_to_next, mhe_add of the plaintext; buffers allocated once) against one mhe_encrypt_pk_batch;
 words compared first, interleaved rounds (enc_bench).
+keyseqD / keybatchD (--ops keygen --keygen D,...): one key-switching key of D digits (D = K - 1: a full
+key; fewer: a level-truncated one) -- per digit the sequence seal's make_kswitch_key_seq issues
+(mhe_prng_uniform_bulk with the download of its reject count and the host synchronisation, and for a
+digit with rejected words the second download, the host's ordered walk of the stream tail, the upload
+and mhe_prng_apply_fixes with its synchronisation; mhe_prng_small, mhe_ntt_forward, mhe_multiply_plain, mhe_add, mhe_negate, mhe_multiply_scalar, mhe_add,
+and four device copies for a truncated key; buffers allocated once, which spares the sequence its three
+stream-ordered allocations per digit) against one mhe_encrypt_sk_batch; words compared first, interleaved
+rounds timed on the host clock, since the sequence synchronises (key_bench).
 Used for A/B runs of library variants (MHE_LIB_PATH=build/var/NAME/libmhe.so).
 
     python scripts/ubench_ops.py [--limbs 31] [--reps 50]
@@ -156,6 +164,101 @@ def enc_bench(eng, rnd, L, n, B, reps, rounds, st):
                       "ratio": round(med["encbatch"] / med["encseq"], 4)}), flush=True)
 
 
+def key_bench(eng, rnd, moduli, n, D, reps, rounds):
+    """keyseq against keybatch for one key of D digits over the context's K primes.  The legs' words
+    are compared first; then `rounds` interleaved rounds of `reps` keys after one warm-up, each round
+    timed on the host clock from a drained device to a drained device.  One JSON line per leg and
+    round, then one with the medians and each leg's spread (max - min over its rounds)."""
+    import ctypes
+    import time
+
+    K, KL = eng.K, D + 1
+    full = KL == K
+    lib, h = mhe.lib(), eng._h
+    sk, nk = rnd(K, n, limbs=K), rnd(K, n, limbs=K)
+    seeds = [[200 + j, 2, 3, 4, 5, 6, 7, 8] for j in range(D)]
+    # the public seed of a: the first 64 bytes of the bootstrap stream, as the host derives it
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import oracle as O
+
+    pub = [np.frombuffer(O.prng_bytes(sd, 64), dtype=np.uint64).copy() for sd in seeds]
+    # the first words after the bulk of a's stream, for the host walk of a digit with rejected words
+    # (seal's StreamReader computes them on the host as it walks; here once, outside the timed region)
+    tails = [np.frombuffer(O.prng_bytes([int(w) for w in pb], (K * n + 1024) * 8), dtype=np.uint64)[K * n:].copy()
+             for pb in pub]
+    mmul = [(1 << 64) - 1 - (((1 << 64) - 1) % int(qi)) - 1 for qi in moduli]
+    idx = np.arange(K, dtype=np.int32)
+    idx_p = idx.ctypes.data_as(ctypes.c_void_p)
+    cap = 1 << 16
+    rej = torch.zeros(cap, dtype=torch.int64, device=eng.torch_device)
+    cnt = torch.zeros(1, dtype=torch.int32, device=eng.torch_device)
+    key_seq, key_bat = eng.empty(D, 2, KL, n), eng.empty(D, 2, KL, n)
+    tmp, t = eng.empty(2, K, n), eng.empty(K, n)
+    def keyseq():
+        for j in range(D):
+            c = key_seq[j] if full else tmp
+            cnt.zero_()
+            rc = lib.mhe_prng_uniform_bulk(h, pub[j].ctypes.data_as(ctypes.c_void_p), K, idx_p, idx_p, c[1].data_ptr(),
+                                           rej.data_ptr(), cnt.data_ptr(), cap, eng.stream())
+            if rc:
+                raise SystemExit(mhe.lib().mhe_last_error().decode())
+            count = int(cnt.item())  # the download and the host synchronisation
+            if count:
+                # rnd::sample_uniform_host_walk: the indices come back, are ordered and redrawn in turn
+                tail, ti, fixes = tails[j], 0, []
+                for g in sorted(rej[:count].cpu().tolist()):
+                    l = g // n
+                    while int(tail[ti]) >= mmul[l]:
+                        ti += 1
+                    fixes += [l * n + g % n, int(tail[ti]) % int(moduli[l])]
+                    ti += 1
+                fx = torch.from_numpy(np.array(fixes, np.uint64).view(np.int64)).to(eng.torch_device)
+                if lib.mhe_prng_apply_fixes(h, fx.data_ptr(), count, c[1].data_ptr(), eng.stream()):
+                    raise SystemExit(mhe.lib().mhe_last_error().decode())
+                torch.cuda.synchronize()  # the host fix list is temporary
+            eng.prng_small("cbd", K, seeds[j], 64, out=c[0])
+            eng.ntt_forward(c[0], lazy=True)
+            eng.multiply_plain(sk, c[1], out=t)
+            eng.add(t, c[0], out=c[0])
+            eng.negate(c[0], out=c[0])
+            f = [0] * K
+            f[j] = P % q[j]
+            eng.multiply_scalar(nk, f, out=t)
+            eng.add(c[0], t, out=c[0])
+            if not full:
+                for p in range(2):
+                    key_seq[j, p, :D].copy_(tmp[p, :D])
+                    key_seq[j, p, D].copy_(tmp[p, K - 1])
+
+    def keybatch():
+        eng.encrypt_sk_batch(seeds, sk, K, D, 1, [nk] * D, list(range(D)), outs=[key_bat[j] for j in range(D)])
+
+    q, P = moduli, moduli[-1]
+    legs = {"keyseq": keyseq, "keybatch": keybatch}
+    keyseq()
+    keybatch()
+    torch.cuda.synchronize()
+    if not torch.equal(key_seq, key_bat):
+        raise SystemExit(f"keyseq and keybatch differ at {D} digits")
+    us = {k: [] for k in legs}
+    for r in range(rounds):
+        for name, f in legs.items():
+            f()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                f()
+            torch.cuda.synchronize()
+            us[name].append((time.perf_counter() - t0) * 1e6 / reps)
+            print(json.dumps({"op": f"{name}{D}", "limbs": K, "round": r, "us": round(us[name][-1], 2)}), flush=True)
+    med = {k: float(np.median(v)) for k, v in us.items()}
+    print(json.dumps({"op": f"keygen{D}", "limbs": K, "words_equal": True, "key_bytes": D * 2 * KL * n * 8,
+                      "keyseq_us": round(med["keyseq"], 2), "keybatch_us": round(med["keybatch"], 2),
+                      "keyseq_spread_us": round(max(us["keyseq"]) - min(us["keyseq"]), 2),
+                      "keybatch_spread_us": round(max(us["keybatch"]) - min(us["keybatch"]), 2),
+                      "ratio": round(med["keybatch"] / med["keyseq"], 4)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--limbs", type=int, default=31)
@@ -169,6 +272,8 @@ def main():
     ap.add_argument("--prod-reps", type=int, default=20, help="calls per timed round of prodseq / prodsum")
     ap.add_argument("--rounds", type=int, default=3, help="interleaved rounds of prodseq / prodsum / encrypt")
     ap.add_argument("--encrypt", default="8,1", help="entries per call of the encrypt op, comma-separated")
+    ap.add_argument("--keygen", default="31,12", help="digits per key of the keygen op, comma-separated")
+    ap.add_argument("--key-reps", type=int, default=5, help="keys per timed round of keyseq / keybatch")
     a = ap.parse_args()
     log_n, n = 16, 1 << 16
     bits = [51] + [46] * 16 + [51] * 14 + [51]
@@ -186,6 +291,11 @@ def main():
         return torch.remainder(g, q)
 
     st = torch.cuda.current_stream(eng.torch_device)
+    if a.ops == "keygen":
+        # on its own: the keys it makes are the large buffers
+        for D in a.keygen.split(","):
+            key_bench(eng, rnd, moduli, n, int(D), a.key_reps, a.rounds)
+        return
     if a.ops == "encrypt":
         # on its own: none of the key-switching keys the other ops need
         for B in a.encrypt.split(","):
