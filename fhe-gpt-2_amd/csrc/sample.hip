@@ -23,8 +23,12 @@
 //     on the stream, no host round trip.
 //   sample_poly_cbd (rlwe.cpp:101-133): 6 bytes per coefficient, x[2], x[5] masked to 5 bits,
 //     noise = pop(x0)+pop(x1)+pop(x2) - pop(x3)-pop(x4)-pop(x5).
-// Small samples are written as canonical residues over every requested limb (rand + (flag & q));
-// the batched encryption's samplers (k_enc_*) write one signed byte per coefficient instead.
+// Each sampler has two kernels, which differ only in where a value goes: the single-seed kernels
+// (k_prng_*) write canonical residues over every requested limb (rand + (flag & q)), the batched ones
+// (k_enc_*, k_sk_cbd, k_uni_bulk; the entry comes from the grid) one signed byte per coefficient, or
+// the uniform words with a bit plane of the rejects.  What is computed exists once, in the device
+// functions both kernels of a pair call (ternary_wg, ternary_walk, cbd_bytes_wg, expand_residues,
+// uniform_bulk_wg); a kernel keeps its addressing and its store.
 #include <hip/hip_runtime.h>
 
 #include "../../include/mhe.h"
@@ -86,99 +90,109 @@ __device__ __forceinline__ void stream_block(const Seed &s, u64 blk, u64 (&out)[
     b2b::xof_block(root, (u32)(blk & 63), b2b::kPrngBuffer, 64, out);
 }
 
-// Bulk of sample_poly_uniform over `limbs` limbs: one thread per 64-byte block (8 words), a
-// workgroup's 256 blocks in 4 buffers.
-__global__ __launch_bounds__(256) void k_prng_uniform(Seed s, LimbMap map, u64 *out, const PrimeDev *primes, int limbs,
-                                                      int log_n, u64 *rej, u32 *rej_count, u32 rej_cap)
+// A batch of entries, at most MHE_SAMPLE_MAXB per launch: the entry comes from the grid; its seed, its
+// plane of signed bytes (small + entry * pitch) and its state words are its own.
+constexpr int MHE_SAMPLE_MAXB = 8; // ntt.h MHE_MAXB (encrypt.h asserts it fits)
+struct SeedB
 {
-    __shared__ u64 roots[kMaxRoots][8];
-    const u64 b0 = (u64)blockIdx.x * 256, blk = b0 + threadIdx.x;
-    const u64 total = (u64)limbs << log_n;
-    const u64 last = ((total / 8 < b0 + 256) ? total / 8 : b0 + 256) - 1;
-    load_roots(s, b0 >> 6, (int)((last >> 6) - (b0 >> 6) + 1), roots);
-    if (blk * 8 >= total) return;
-    u64 w[8];
-    block_from_roots(roots, b0 >> 6, blk, w);
-#pragma unroll
-    for (int k = 0; k < 8; k++)
-    {
-        const u64 g = blk * 8 + k;
-        const int l = (int)(g >> log_n);
-        const PrimeDev p = primes[map.prime[l]];
-        // max_multiple = (2^64 - 1) - barrett_reduce_64(2^64 - 1, q) - 1 (rlwe.cpp:152)
-        const u64 mm = ~0ULL - barrett64(~0ULL, p) - 1;
-        if (w[k] >= mm)
-        {
-            const u32 at = atomicAdd(rej_count, 1u);
-            if (at < rej_cap) rej[at] = g;
-        }
-        else if (map.slot[l] >= 0)
-            out[((u64)map.slot[l] << log_n) + (g & (((u64)1 << log_n) - 1))] = barrett64(w[k], p);
-    }
+    Seed s[MHE_SAMPLE_MAXB];
+};
+struct UniB
+{
+    SeedB sb;
+    u64 *out[MHE_SAMPLE_MAXB];
+};
+
+// a small signed value as a canonical residue mod q
+__device__ __forceinline__ u64 small_residue(int v, u64 q)
+{
+    return v >= 0 ? (u64)v : q - (u64)(-v);
 }
 
-__global__ void k_prng_apply(const u64 *fix, u32 count, u64 *out)
+// Signed bytes val[0, cnt) in LDS as residues of limbs blockIdx.y, blockIdx.y + gridDim.y, ... (every
+// y computes the same values; the limbs split keeps the grid wide), coalesced; `out` is the
+// workgroup's first coefficient in limb 0.
+__device__ __forceinline__ void expand_residues(const signed char *val, u32 cnt, u64 *out, const PrimeDev *primes,
+                                                int limbs, int log_n)
 {
-    const u32 i = blockIdx.x * 256 + threadIdx.x;
-    if (i < count) out[fix[2 * i]] = fix[2 * i + 1];
-}
-
-// sample_poly_ternary: coefficients [0, n) from the stream bytes at byte offset `off` (64-aligned).
-// A workgroup owns 256 stream blocks (4096 coefficients): one thread per block draws its 16 values
-// into LDS, then the workgroup writes them coalesced to the limbs blockIdx.y, blockIdx.y +
-// gridDim.y, ... (every y redraws the same values; the limbs split keeps the grid wide).  A zero word
-// would be redrawn (Lemire); those are counted in state[1] (by y == 0) and k_prng_ternary_fix redoes
-// the poly sequentially.
-__global__ __launch_bounds__(256) void k_prng_ternary(Seed s, u64 off, u64 *out, const PrimeDev *primes, int limbs,
-                                                      int log_n, u32 *state)
-{
-    __shared__ u64 roots[kMaxRoots][8];
-    __shared__ unsigned char val[256 * 16];
-    const u64 n = (u64)1 << log_n;
-    const u64 nblk = n / 16, wb0 = (u64)blockIdx.x * 256;
-    const u64 wg_end = (wb0 + 256 < nblk ? wb0 + 256 : nblk);
-    const u64 first = (off >> 6) + wb0, last = (off >> 6) + wg_end - 1;
-    load_roots(s, first >> 6, (int)((last >> 6) - (first >> 6) + 1), roots);
-    if (wb0 + threadIdx.x < wg_end)
-    {
-        u64 w[8];
-        block_from_roots(roots, first >> 6, first + threadIdx.x, w);
-#pragma unroll
-        for (int k = 0; k < 16; k++)
-        {
-            const u32 g = (u32)(w[k >> 1] >> (32 * (k & 1)));
-            if (g == 0 && blockIdx.y == 0) atomicAdd(&state[1], 1u);
-            val[threadIdx.x * 16 + k] = (unsigned char)(((u64)g * 3) >> 32); // {0, 1, 2} -> {-1, 0, 1}
-        }
-    }
-    __syncthreads();
-    const u32 cnt = (u32)((wg_end - wb0) * 16);
     for (int l = blockIdx.y; l < limbs; l += gridDim.y)
     {
         const u64 q = primes[l].q;
-        u64 *o = out + ((u64)l << log_n) + wb0 * 16;
-        for (u32 i = threadIdx.x; i < cnt; i += 256)
-        {
-            const u32 r = val[i];
-            o[i] = r == 0 ? q - 1 : r - 1;
-        }
+        u64 *o = out + ((u64)l << log_n);
+        for (u32 i = threadIdx.x; i < cnt; i += 256) o[i] = small_residue(val[i], q);
     }
 }
 
-// The rare redraw path of sample_poly_ternary (probability ~ n 2^-32 per poly): one thread walks
-// the stream 4 bytes at a time, skipping zero words as libstdc++ 11's uniform_int_distribution
-// does for a 32-bit URBG (threshold 2^32 mod 3 = 1), and records in state[0] how many bytes the
-// redraws consumed, which moves the offsets of the samples drawn after it.
-__global__ void k_prng_ternary_fix(Seed s, u64 off, u64 *out, const PrimeDev *primes, int limbs, int log_n,
-                                   u32 *state)
+// ------------------------------------------------------------------------ sample_poly_ternary
+// libstdc++ 11's uniform_int_distribution(0, 2) of a nonzero 32-bit word (Lemire), less one
+__device__ __forceinline__ int ternary_of(u32 g)
 {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    if (state[1] == 0)
+    return (int)(((u64)g * 3) >> 32) - 1;
+}
+
+// Coefficients [0, n) from the stream bytes at byte offset `off` (64-aligned).  Workgroup blockIdx.x
+// owns 256 stream blocks (4096 coefficients) and thread t the 16 values of block t of those: they
+// come back as signed bytes in pk, with the number of zero words among the 16 -- those would be
+// redrawn, so a poly that has one is redone by ternary_walk.  False: the block is past the poly.
+__device__ __forceinline__ bool ternary_wg(const Seed &s, u64 off, int log_n, u32 (&pk)[4], u32 &zeros)
+{
+    __shared__ u64 roots[kMaxRoots][8];
+    const u64 nblk = ((u64)1 << log_n) / 16, wb0 = (u64)blockIdx.x * 256;
+    const u64 wg_end = (wb0 + 256 < nblk ? wb0 + 256 : nblk);
+    const u64 first = (off >> 6) + wb0, last = (off >> 6) + wg_end - 1;
+    load_roots(s, first >> 6, (int)((last >> 6) - (first >> 6) + 1), roots);
+    if (wb0 + threadIdx.x >= wg_end) return false;
+    u64 w[8];
+    block_from_roots(roots, first >> 6, first + threadIdx.x, w);
+    zeros = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) pk[k] = 0;
+#pragma unroll
+    for (int k = 0; k < 16; k++)
     {
-        state[0] = 0;
-        return;
+        const u32 g = (u32)(w[k >> 1] >> (32 * (k & 1)));
+        zeros += g == 0;
+        pk[k >> 2] |= ((u32)ternary_of(g) & 0xffu) << (8 * (k & 3));
     }
-    const u64 n = (u64)1 << log_n;
+    return true;
+}
+
+// Residues over `limbs` limbs; the zero words are counted in state[1] (by y == 0).
+__global__ __launch_bounds__(256) void k_prng_ternary(Seed s, u64 off, u64 *out, const PrimeDev *primes, int limbs,
+                                                      int log_n, u32 *state)
+{
+    __shared__ uint4 val[256];
+    u32 pk[4], zeros;
+    if (ternary_wg(s, off, log_n, pk, zeros))
+    {
+        if (zeros && blockIdx.y == 0) atomicAdd(&state[1], zeros);
+        val[threadIdx.x] = make_uint4(pk[0], pk[1], pk[2], pk[3]);
+    }
+    __syncthreads();
+    const u64 n = (u64)1 << log_n, c0 = (u64)blockIdx.x * 4096;
+    expand_residues(reinterpret_cast<const signed char *>(val), (u32)((n - c0) < 4096 ? (n - c0) : 4096), out + c0,
+                    primes, limbs, log_n);
+}
+
+// u of entry blockIdx.y (stream byte 0): a thread's 16 values leave as one 16-byte store; the zero
+// words are counted in state[entry][1].
+__global__ __launch_bounds__(256) void k_enc_ternary(SeedB sb, signed char *small, size_t pitch, int log_n, u32 *state)
+{
+    const int ent = blockIdx.y;
+    u32 pk[4], zeros;
+    if (!ternary_wg(sb.s[ent], 0, log_n, pk, zeros)) return;
+    if (zeros) atomicAdd(&state[2 * ent + 1], zeros);
+    uint4 *o = reinterpret_cast<uint4 *>(small + (size_t)ent * pitch) + (u64)blockIdx.x * 256 + threadIdx.x;
+    *o = make_uint4(pk[0], pk[1], pk[2], pk[3]);
+}
+
+// The rare redraw path (probability ~ n 2^-32 per poly): one thread walks the stream 4 bytes at a
+// time from byte `off`, skipping zero words as libstdc++ 11's uniform_int_distribution does for a
+// 32-bit URBG (threshold 2^32 mod 3 = 1), and hands value i to put(i, v).  Returns how many bytes
+// the redraws consumed, which moves the offsets of the samples drawn after this one.
+template <class Put>
+__device__ __forceinline__ u32 ternary_walk(const Seed &s, u64 off, u64 n, Put put)
+{
     u64 pos = off, cached = ~0ULL, w[8];
     for (u64 i = 0; i < n; i++)
     {
@@ -194,107 +208,28 @@ __global__ void k_prng_ternary_fix(Seed s, u64 off, u64 *out, const PrimeDev *pr
             g = (u32)(w[(pos & 63) >> 3] >> (32 * ((pos >> 2) & 1)));
             pos += 4;
         } while (g == 0);
-        const u64 r = ((u64)g * 3) >> 32;
-        for (int l = 0; l < limbs; l++)
-        {
-            const u64 q = primes[l].q;
-            out[((u64)l << log_n) + i] = r == 0 ? q - 1 : r - 1;
-        }
+        put(i, ternary_of(g));
     }
-    state[0] = (u32)(pos - off - 4 * n);
+    return (u32)(pos - off - 4 * n);
 }
 
-// sample_poly_cbd: coefficients [0, n) from the bytes at offset off + (*extra when given), a
-// multiple of 4.  A workgroup owns kCbdCoeffs coefficients (6 bytes each): it computes the roots
-// of the <= 3 buffers and the <= 97 stream blocks those bytes span into LDS (one compression per
-// block), forms the noise values in LDS, and writes them coalesced to the limbs blockIdx.y,
-// blockIdx.y + gridDim.y, ... (as k_prng_ternary).
-constexpr int kCbdCoeffs = 1024;
-constexpr int kCbdBlocks = (6 * kCbdCoeffs) / 64 + 1;
-__global__ __launch_bounds__(256) void k_prng_cbd(Seed s, u64 off, const u32 *extra, u64 *out, const PrimeDev *primes,
-                                                  int limbs, int log_n)
+// Both fix kernels return at once for a poly without a zero word (state[1] == 0) and leave the bytes
+// consumed in state[0].
+__global__ void k_prng_ternary_fix(Seed s, u64 off, u64 *out, const PrimeDev *primes, int limbs, int log_n,
+                                   u32 *state)
 {
-    __shared__ u64 roots[kMaxRoots][8];
-    __shared__ u64 bytes[kCbdBlocks * 8];
-    __shared__ signed char noise[kCbdCoeffs];
-    const u64 n = (u64)1 << log_n;
-    const u64 c0 = (u64)blockIdx.x * kCbdCoeffs;
-    const u64 cnt = (n - c0) < (u64)kCbdCoeffs ? (n - c0) : (u64)kCbdCoeffs;
-    const u64 start = off + (extra ? extra[0] : 0) + 6 * c0;
-    const u64 b0 = start >> 6, b1 = (start + 6 * cnt - 1) >> 6;
-    load_roots(s, b0 >> 6, (int)((b1 >> 6) - (b0 >> 6) + 1), roots);
-    if (threadIdx.x <= b1 - b0)
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (state[1] == 0)
     {
-        u64 w[8];
-        block_from_roots(roots, b0 >> 6, b0 + threadIdx.x, w);
-#pragma unroll
-        for (int k = 0; k < 8; k++) bytes[threadIdx.x * 8 + k] = w[k];
+        state[0] = 0;
+        return;
     }
-    __syncthreads();
-    const u32 skip = (u32)(start - 64 * b0);
-    auto byte_at = [&](u32 i) -> u32 {
-        i += skip;
-        return (u32)(bytes[i >> 3] >> (8 * (i & 7))) & 0xff;
-    };
-    for (u32 k = threadIdx.x; k < cnt; k += 256)
-    {
-        const u32 c = 6 * k;
-        noise[k] = (signed char)(__popc(byte_at(c)) + __popc(byte_at(c + 1)) + __popc(byte_at(c + 2) & 0x1f) -
-                                 __popc(byte_at(c + 3)) - __popc(byte_at(c + 4)) - __popc(byte_at(c + 5) & 0x1f));
-    }
-    __syncthreads();
-    for (int l = blockIdx.y; l < limbs; l += gridDim.y)
-    {
-        const u64 q = primes[l].q;
-        u64 *o = out + ((u64)l << log_n) + c0;
-        for (u32 k = threadIdx.x; k < cnt; k += 256)
-        {
-            const int v = noise[k];
-            o[k] = v >= 0 ? (u64)v : q - (u64)(-v);
-        }
-    }
+    state[0] = ternary_walk(s, off, (u64)1 << log_n, [&](u64 i, int v) {
+        for (int l = 0; l < limbs; l++) out[((u64)l << log_n) + i] = small_residue(v, primes[l].q);
+    });
 }
 
-// ------------------------------------------------------------------ batched encryption samples
-// The three small polys of a public-key encryption (encrypt_zero_asymmetric, rlwe.cpp:220-286) for a
-// batch of entries, one signed byte per coefficient: small[entry][3][n], entries `pitch` bytes apart,
-// = u (ternary, stream byte 0), e_0 and e_1 (CBD, bytes 4n and 10n plus what the entry's ternary
-// redraws consumed).  The residues
-// mod each prime are expanded where they are used (jobs.h, the encryption jobs).  The entry comes
-// from the grid; its seed and its redraw state[entry][2] (as k_prng_ternary's) are its own.
-constexpr int MHE_SAMPLE_MAXB = 8; // entries per launch: ntt.h MHE_MAXB (encrypt.h asserts it fits)
-struct SeedB
-{
-    Seed s[MHE_SAMPLE_MAXB];
-};
-
-// k_prng_ternary for entry blockIdx.y: a thread's 16 values leave as one 16-byte store.
-__global__ __launch_bounds__(256) void k_enc_ternary(SeedB sb, signed char *small, size_t pitch, int log_n, u32 *state)
-{
-    __shared__ u64 roots[kMaxRoots][8];
-    const int ent = blockIdx.y;
-    const u64 n = (u64)1 << log_n;
-    const u64 nblk = n / 16, wb0 = (u64)blockIdx.x * 256;
-    const u64 wg_end = (wb0 + 256 < nblk ? wb0 + 256 : nblk);
-    load_roots(sb.s[ent], wb0 >> 6, (int)(((wg_end - 1) >> 6) - (wb0 >> 6) + 1), roots);
-    if (wb0 + threadIdx.x >= wg_end) return;
-    u64 w[8];
-    block_from_roots(roots, wb0 >> 6, wb0 + threadIdx.x, w);
-    u32 pk[4] = { 0, 0, 0, 0 }, zeros = 0;
-#pragma unroll
-    for (int k = 0; k < 16; k++)
-    {
-        const u32 g = (u32)(w[k >> 1] >> (32 * (k & 1)));
-        zeros += g == 0;
-        const u32 v = (u32)(((u64)g * 3) >> 32) - 1u; // {0, 1, 2} -> {-1, 0, 1}
-        pk[k >> 2] |= (v & 0xffu) << (8 * (k & 3));
-    }
-    if (zeros) atomicAdd(&state[2 * ent + 1], zeros);
-    uint4 *o = reinterpret_cast<uint4 *>(small + (size_t)ent * pitch) + wb0 + threadIdx.x;
-    *o = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-}
-
-// k_prng_ternary_fix per entry (workgroup = entry): returns at once for an entry without a zero word.
+// workgroup = entry
 __global__ void k_enc_ternary_fix(SeedB sb, signed char *small, size_t pitch, int log_n, u32 *state)
 {
     const int ent = blockIdx.x;
@@ -304,34 +239,27 @@ __global__ void k_enc_ternary_fix(SeedB sb, signed char *small, size_t pitch, in
         state[2 * ent] = 0;
         return;
     }
-    const u64 n = (u64)1 << log_n;
     signed char *o = small + (size_t)ent * pitch;
-    u64 pos = 0, cached = ~0ULL, w[8];
-    for (u64 i = 0; i < n; i++)
-    {
-        u32 g;
-        do
-        {
-            const u64 blk = pos >> 6;
-            if (blk != cached)
-            {
-                stream_block(sb.s[ent], blk, w);
-                cached = blk;
-            }
-            g = (u32)(w[(pos & 63) >> 3] >> (32 * ((pos >> 2) & 1)));
-            pos += 4;
-        } while (g == 0);
-        o[i] = (signed char)((int)(((u64)g * 3) >> 32) - 1);
-    }
-    state[2 * ent] = (u32)(pos - 4 * n);
+    state[2 * ent] = ternary_walk(sb.s[ent], 0, (u64)1 << log_n, [&](u64 i, int v) { o[i] = (signed char)v; });
 }
 
-// k_prng_cbd's noise values of coefficients [c0, c0 + cnt) (cnt <= kCbdCoeffs, a multiple of 4) from
-// the stream bytes at `start` on, one signed byte each: a thread's 4 values leave as one dword of o.
-__device__ __forceinline__ void cbd_bytes_wg(const Seed &s, u64 start, u64 cnt, u32 *o)
+// ---------------------------------------------------------------------------- sample_poly_cbd
+// A workgroup owns kCbdCoeffs coefficients (6 bytes each): it computes the roots of the <= 3 buffers
+// and the <= 97 stream blocks those bytes span into LDS (one compression per block).
+constexpr int kCbdCoeffs = 1024;
+constexpr int kCbdBlocks = (6 * kCbdCoeffs) / 64 + 1;
+
+// Workgroup blockIdx.x's noise values, coefficients [c0, c0 + cnt) of a poly whose bytes start at
+// stream byte `first` (a multiple of 4), one signed byte each: a thread's 4 values leave as one dword
+// of o (global or LDS).  Returns cnt, a multiple of 4: n is a power of two from 2^12 to 2^16 in every
+// context, and the entry points refuse n < 32.
+__device__ __forceinline__ u32 cbd_bytes_wg(const Seed &s, u64 first, int log_n, u32 *o)
 {
     __shared__ u64 roots[kMaxRoots][8];
     __shared__ u64 bytes[kCbdBlocks * 8];
+    const u64 n = (u64)1 << log_n, c0 = (u64)blockIdx.x * kCbdCoeffs;
+    const u32 cnt = (u32)((n - c0) < (u64)kCbdCoeffs ? (n - c0) : (u64)kCbdCoeffs);
+    const u64 start = first + 6 * c0;
     const u64 b0 = start >> 6, b1 = (start + 6 * cnt - 1) >> 6;
     load_roots(s, b0 >> 6, (int)((b1 >> 6) - (b0 >> 6) + 1), roots);
     if (threadIdx.x <= b1 - b0)
@@ -347,7 +275,7 @@ __device__ __forceinline__ void cbd_bytes_wg(const Seed &s, u64 start, u64 cnt, 
         i += skip;
         return (u32)(bytes[i >> 3] >> (8 * (i & 7))) & 0xff;
     };
-    if (4 * threadIdx.x >= cnt) return;
+    if (4 * threadIdx.x >= cnt) return cnt;
     u32 pk = 0;
 #pragma unroll
     for (int k = 0; k < 4; k++)
@@ -358,61 +286,70 @@ __device__ __forceinline__ void cbd_bytes_wg(const Seed &s, u64 start, u64 cnt, 
         pk |= ((u32)v & 0xffu) << (8 * k);
     }
     o[threadIdx.x] = pk;
+    return cnt;
 }
 
-// k_prng_cbd for error poly j = blockIdx.y of entry blockIdx.z, from byte 4n + 6n j + the entry's
-// extra bytes.
+// Residues over `limbs` limbs, from the bytes at off + (*extra when given).
+__global__ __launch_bounds__(256) void k_prng_cbd(Seed s, u64 off, const u32 *extra, u64 *out, const PrimeDev *primes,
+                                                  int limbs, int log_n)
+{
+    __shared__ u32 noise[kCbdCoeffs / 4];
+    const u32 cnt = cbd_bytes_wg(s, off + (extra ? extra[0] : 0), log_n, noise);
+    __syncthreads();
+    expand_residues(reinterpret_cast<const signed char *>(noise), cnt, out + (u64)blockIdx.x * kCbdCoeffs, primes, limbs,
+                    log_n);
+}
+
+// The errors of a public-key encryption (encrypt_zero_asymmetric, rlwe.cpp:220-286): small[entry][3][n]
+// = u (k_enc_ternary), e_0, e_1; e_j (j = blockIdx.y) of entry blockIdx.z from byte 4n + 6n j + what
+// the entry's ternary redraws consumed.  The residues mod each prime are expanded where they are used
+// (jobs.h, the encryption jobs).
 __global__ __launch_bounds__(256) void k_enc_cbd(SeedB sb, signed char *small, size_t pitch, int log_n, const u32 *state)
 {
     const int j = blockIdx.y, ent = blockIdx.z;
     const u64 n = (u64)1 << log_n;
-    const u64 c0 = (u64)blockIdx.x * kCbdCoeffs;
-    const u64 cnt = (n - c0) < (u64)kCbdCoeffs ? (n - c0) : (u64)kCbdCoeffs; // a multiple of 4
-    const u64 start = 4 * n + 6 * n * (u64)j + state[2 * ent] + 6 * c0;
-    cbd_bytes_wg(sb.s[ent], start, cnt, reinterpret_cast<u32 *>(small + (size_t)ent * pitch + (size_t)(1 + j) * n + c0));
+    signed char *e = small + (size_t)ent * pitch + (size_t)(1 + j) * n;
+    cbd_bytes_wg(sb.s[ent], 4 * n + 6 * n * (u64)j + state[2 * ent], log_n,
+                 reinterpret_cast<u32 *>(e + (size_t)blockIdx.x * kCbdCoeffs));
 }
 
 // The error of a symmetric encryption (encrypt_zero_symmetric, rlwe.cpp:289-373) of entry blockIdx.y:
-// CBD from stream byte 64 (the first 64 bytes seed the PRNG of a), plane small + entry * pitch.
+// from stream byte 64 (the first 64 bytes seed the PRNG of a), plane small + entry * pitch.
 __global__ __launch_bounds__(256) void k_sk_cbd(SeedB sb, signed char *small, size_t pitch, int log_n)
 {
-    const int ent = blockIdx.y;
-    const u64 n = (u64)1 << log_n;
-    const u64 c0 = (u64)blockIdx.x * kCbdCoeffs;
-    const u64 cnt = (n - c0) < (u64)kCbdCoeffs ? (n - c0) : (u64)kCbdCoeffs;
-    cbd_bytes_wg(sb.s[ent], 64 + 6 * c0, cnt, reinterpret_cast<u32 *>(small + (size_t)ent * pitch + c0));
+    signed char *e = small + (size_t)blockIdx.y * pitch;
+    cbd_bytes_wg(sb.s[blockIdx.y], 64, log_n, reinterpret_cast<u32 *>(e + (size_t)blockIdx.x * kCbdCoeffs));
 }
 
-// ------------------------------------------------------ sample_poly_uniform, all on the device
-// For a batch of entries (seed, output) that share the limb maps.  state[entry][2] (zeroed before the
-// bulk): [0] nonzero when the bulk rejected a word, [1] nonzero when the redraw buffer overflowed.
-struct UniB
+// ------------------------------------------------------------------------ sample_poly_uniform
+// max_multiple = (2^64 - 1) - barrett_reduce_64(2^64 - 1, q) - 1 (rlwe.cpp:152)
+__device__ __forceinline__ u64 max_multiple(const PrimeDev &p)
 {
-    Seed s[MHE_SAMPLE_MAXB];
-    u64 *out[MHE_SAMPLE_MAXB];
-};
+    return ~0ULL - barrett64(~0ULL, p) - 1;
+}
 
-// k_prng_uniform for entry blockIdx.y.  Thread t of a workgroup owns words 8t .. 8t+7 of the
-// workgroup's 2048 (all in one limb: n >= 8) and leaves their reject bits as byte `blk` of the entry's
-// bit plane: bit g of the plane is word g of the stream, so the plane holds the rejects in stream order.
-__global__ __launch_bounds__(256) void k_uni_bulk(UniB ub, LimbMap map, const PrimeDev *primes, int limbs, int log_n,
-                                                  unsigned char *flags, size_t flag_pitch, u32 *state)
+// The bulk over `limbs` limbs: one thread per 64-byte stream block `blk` (8 words, all in one limb:
+// n >= 8), a workgroup's 256 blocks in 4 buffers.  A word below its limb's max_multiple is reduced into
+// the limb's slot of `out` when the limb is kept; the others are bits of rej (bit k: word 8 blk + k).
+// False: the block is past the bulk.
+__device__ __forceinline__ bool uniform_bulk_wg(const Seed &s, const LimbMap &map, u64 *out, const PrimeDev *primes,
+                                                int limbs, int log_n, u64 &blk, u32 &rej)
 {
     __shared__ u64 roots[kMaxRoots][8];
-    const int ent = blockIdx.y;
-    const u64 b0 = (u64)blockIdx.x * 256, blk = b0 + threadIdx.x;
+    const u64 b0 = (u64)blockIdx.x * 256;
     const u64 total = (u64)limbs << log_n;
     const u64 last = ((total / 8 < b0 + 256) ? total / 8 : b0 + 256) - 1;
-    load_roots(ub.s[ent], b0 >> 6, (int)((last >> 6) - (b0 >> 6) + 1), roots);
-    if (blk * 8 >= total) return;
+    load_roots(s, b0 >> 6, (int)((last >> 6) - (b0 >> 6) + 1), roots);
+    blk = b0 + threadIdx.x;
+    if (blk * 8 >= total) return false;
     u64 w[8];
     block_from_roots(roots, b0 >> 6, blk, w);
     const int l = (int)((blk * 8) >> log_n);
     const PrimeDev p = primes[map.prime[l]];
-    const u64 mm = ~0ULL - barrett64(~0ULL, p) - 1; // max_multiple (rlwe.cpp:152)
+    const u64 mm = max_multiple(p);
     const int slot = map.slot[l];
-    u64 *o = ub.out[ent] + ((u64)(slot < 0 ? 0 : slot) << log_n) + ((blk * 8) & (((u64)1 << log_n) - 1));
-    u32 rej = 0;
+    u64 *o = out + ((u64)(slot < 0 ? 0 : slot) << log_n) + ((blk * 8) & (((u64)1 << log_n) - 1));
+    rej = 0;
 #pragma unroll
     for (int k = 0; k < 8; k++)
     {
@@ -421,6 +358,43 @@ __global__ __launch_bounds__(256) void k_uni_bulk(UniB ub, LimbMap map, const Pr
         else if (slot >= 0)
             o[k] = barrett64(w[k], p);
     }
+    return true;
+}
+
+// The rejected indices go to a list of at most rej_cap entries, in no order (the host sorts it);
+// rej_count counts them all.
+__global__ __launch_bounds__(256) void k_prng_uniform(Seed s, LimbMap map, u64 *out, const PrimeDev *primes, int limbs,
+                                                      int log_n, u64 *rej, u32 *rej_count, u32 rej_cap)
+{
+    u64 blk;
+    u32 m;
+    if (!uniform_bulk_wg(s, map, out, primes, limbs, log_n, blk, m)) return;
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+        if ((m >> k) & 1)
+        {
+            const u32 at = atomicAdd(rej_count, 1u);
+            if (at < rej_cap) rej[at] = blk * 8 + k;
+        }
+}
+
+__global__ void k_prng_apply(const u64 *fix, u32 count, u64 *out)
+{
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    if (i < count) out[fix[2 * i]] = fix[2 * i + 1];
+}
+
+// All of sample_poly_uniform on the device, for a batch of entries (seed, output) that share the limb
+// maps.  state[entry][2] (zeroed before the bulk): [0] nonzero when the bulk rejected a word, [1]
+// nonzero when the redraw buffer overflowed.  Entry blockIdx.y's reject bits are byte `blk` of its bit
+// plane: bit g of the plane is word g of the stream, so the plane holds the rejects in stream order.
+__global__ __launch_bounds__(256) void k_uni_bulk(UniB ub, LimbMap map, const PrimeDev *primes, int limbs, int log_n,
+                                                  unsigned char *flags, size_t flag_pitch, u32 *state)
+{
+    const int ent = blockIdx.y;
+    u64 blk;
+    u32 rej;
+    if (!uniform_bulk_wg(ub.sb.s[ent], map, ub.out[ent], primes, limbs, log_n, blk, rej)) return;
     flags[(size_t)ent * flag_pitch + blk] = (unsigned char)rej;
     if (rej) state[2 * ent] = 1; // every writer stores the same word
 }
@@ -473,7 +447,7 @@ __global__ __launch_bounds__(256) void k_uni_redraw(UniB ub, LimbMap map, const 
     __shared__ u64 roots[kMaxRoots][8];
     __shared__ u32 sh[4];
     __shared__ u64 s_last;
-    const Seed &seed = ub.s[ent];
+    const Seed &seed = ub.sb.s[ent];
     const unsigned char *fl = flags + (size_t)ent * flag_pitch;
     u64 *vals = val + (size_t)ent * val_pitch;
     const u32 n8 = 1u << (log_n - 3); // plane bytes per limb
@@ -487,7 +461,7 @@ __global__ __launch_bounds__(256) void k_uni_redraw(UniB ub, LimbMap map, const 
         wg_excl_scan(c, sh, need);
         if (need == 0) continue;
         const PrimeDev p = primes[map.prime[l]];
-        const u64 mm = ~0ULL - barrett64(~0ULL, p) - 1;
+        const u64 mm = max_multiple(p);
         u32 got = 0;
         while (got < need)
         {
@@ -560,46 +534,60 @@ __global__ __launch_bounds__(256) void k_uni_redraw(UniB ub, LimbMap map, const 
     }
 }
 
+// ---------------------------------------------------------------------------------- host side
+int bad_args()
+{
+    return mhe_internal_fail(MHE_ERR_ARG, "invalid sampling arguments");
+}
+
 int launch_check(const char *what)
 {
     if (hipGetLastError() != hipSuccess) return mhe_internal_fail(MHE_ERR_DEVICE, what);
     return MHE_OK;
 }
-} // namespace
 
-#define MHE_EXPORT extern "C" __attribute__((visibility("default")))
-
-// The samples of B <= MHE_SAMPLE_MAXB encryptions (encrypt.h): small [B][3][n] signed bytes, entry e at
-// small + e * pitch (both multiples of 16), state [B][2] device words.  Three launches and one memset,
-// no host synchronisation.
-int mhe_internal_encrypt_samples(mhe_ctx *c, int B, const uint64_t (*seeds)[8], signed char *small, uint32_t *state,
-                                 size_t pitch, hipStream_t st)
+// what a sampler needs of the context
+struct Primes
 {
-    const PrimeDev *primes;
+    const PrimeDev *dev;
     const uint64_t *q;
     int K, log_n;
-    if (mhe_internal_primes(c, &primes, &q, &K, &log_n)) return mhe_internal_fail(MHE_ERR_ARG, "context is not valid");
-    if (!seeds || !small || !state || B < 1 || B > MHE_SAMPLE_MAXB || log_n < 5 || (((uintptr_t)small | pitch) & 15) ||
-        (B > 1 && pitch < 3 * ((size_t)1 << log_n)))
-        return mhe_internal_fail(MHE_ERR_ARG, "invalid sampling arguments");
+};
+int primes_of(mhe_ctx *c, Primes &P)
+{
+    if (mhe_internal_primes(c, &P.dev, &P.q, &P.K, &P.log_n)) return mhe_internal_fail(MHE_ERR_ARG, "context is not valid");
+    return MHE_OK;
+}
+
+Seed seed_of(const uint64_t w[8])
+{
+    Seed s;
+    for (int i = 0; i < 8; i++) s.w[i] = w[i];
+    return s;
+}
+SeedB seeds_of(int B, const uint64_t (*seeds)[8])
+{
     SeedB sb{};
-    for (int e = 0; e < B; e++)
-        for (int i = 0; i < 8; i++) sb.s[e].w[i] = seeds[e][i];
-    const u64 n = (u64)1 << log_n;
-    if (hipMemsetAsync(state, 0, 8 * (size_t)B, st) != hipSuccess)
-        return mhe_internal_fail(MHE_ERR_DEVICE, "sampling state reset failed");
-    hipLaunchKernelGGL(k_enc_ternary, dim3((unsigned)((n / 16 + 255) / 256), (unsigned)B), dim3(256), 0, st, sb, small,
-                       pitch, log_n, state);
-    hipLaunchKernelGGL(k_enc_ternary_fix, dim3((unsigned)B), dim3(64), 0, st, sb, small, pitch, log_n, state);
-    hipLaunchKernelGGL(k_enc_cbd, dim3((unsigned)((n + kCbdCoeffs - 1) / kCbdCoeffs), 2, (unsigned)B), dim3(256), 0, st,
-                       sb, small, pitch, log_n, (const u32 *)state);
-    return launch_check("sampling kernel launch failed");
+    for (int e = 0; e < B; e++) sb.s[e] = seed_of(seeds[e]);
+    return sb;
+}
+
+// the maps of `limbs` sampled limbs over a context of K primes into m; false when they are not valid
+bool limb_map(int K, int limbs, const int *prime_of_limb, const int *slot_of_limb, LimbMap &m)
+{
+    if (!prime_of_limb || !slot_of_limb || limbs < 1 || limbs > 64) return false;
+    for (int l = 0; l < 64; l++)
+    {
+        if (l < limbs && (prime_of_limb[l] < 0 || prime_of_limb[l] >= K || slot_of_limb[l] < -1 || slot_of_limb[l] > 63))
+            return false;
+        m.slot[l] = l < limbs ? (signed char)slot_of_limb[l] : -1;
+        m.prime[l] = l < limbs ? prime_of_limb[l] : 0;
+    }
+    return true;
 }
 
 // Scratch of the on-device sample_poly_uniform for B entries: state [MHE_SAMPLE_MAXB][2] words, then
 // per entry a reject bit plane of limbs * n bits and `cap` redrawn words (sample_cap.h).
-namespace
-{
 struct UniLayout
 {
     size_t flag_pitch, flags_at, val_at, bytes;
@@ -617,58 +605,65 @@ UniLayout uni_layout(mhe_ctx *c, const uint64_t *q, int B, int limbs, const int 
     u.bytes = u.val_at + (size_t)B * u.cap * sizeof(u64);
     return u;
 }
-bool uni_maps_ok(int K, int log_n, int limbs, const int *prime_of_limb, const int *slot_of_limb)
-{
-    if (!prime_of_limb || !slot_of_limb || limbs < 1 || limbs > 64 || log_n < 5) return false;
-    for (int l = 0; l < limbs; l++)
-        if (prime_of_limb[l] < 0 || prime_of_limb[l] >= K || slot_of_limb[l] < -1 || slot_of_limb[l] > 63) return false;
-    return true;
-}
 } // namespace
+
+#define MHE_EXPORT extern "C" __attribute__((visibility("default")))
+
+// The samples of B <= MHE_SAMPLE_MAXB encryptions (encrypt.h): small [B][3][n] signed bytes, entry e at
+// small + e * pitch (both multiples of 16), state [B][2] device words.  Three launches and one memset,
+// no host synchronisation.
+int mhe_internal_encrypt_samples(mhe_ctx *c, int B, const uint64_t (*seeds)[8], signed char *small, uint32_t *state,
+                                 size_t pitch, hipStream_t st)
+{
+    Primes P;
+    if (int r = primes_of(c, P)) return r;
+    const int log_n = P.log_n;
+    if (!seeds || !small || !state || B < 1 || B > MHE_SAMPLE_MAXB || log_n < 5 || (((uintptr_t)small | pitch) & 15) ||
+        (B > 1 && pitch < 3 * ((size_t)1 << log_n)))
+        return bad_args();
+    const SeedB sb = seeds_of(B, seeds);
+    const u64 n = (u64)1 << log_n;
+    if (hipMemsetAsync(state, 0, 8 * (size_t)B, st) != hipSuccess)
+        return mhe_internal_fail(MHE_ERR_DEVICE, "sampling state reset failed");
+    hipLaunchKernelGGL(k_enc_ternary, dim3((unsigned)((n / 16 + 255) / 256), (unsigned)B), dim3(256), 0, st, sb, small,
+                       pitch, log_n, state);
+    hipLaunchKernelGGL(k_enc_ternary_fix, dim3((unsigned)B), dim3(64), 0, st, sb, small, pitch, log_n, state);
+    hipLaunchKernelGGL(k_enc_cbd, dim3((unsigned)((n + kCbdCoeffs - 1) / kCbdCoeffs), 2, (unsigned)B), dim3(256), 0, st,
+                       sb, small, pitch, log_n, (const u32 *)state);
+    return launch_check("sampling kernel launch failed");
+}
 
 size_t mhe_internal_uniform_scratch_bytes(mhe_ctx *c, int B, int limbs, const int *prime_of_limb)
 {
-    const PrimeDev *primes;
-    const uint64_t *q;
-    int K, log_n;
-    if (mhe_internal_primes(c, &primes, &q, &K, &log_n)) return 0;
-    return uni_layout(c, q, B, limbs, prime_of_limb, log_n).bytes;
+    Primes P;
+    if (primes_of(c, P)) return 0;
+    return uni_layout(c, P.q, B, limbs, prime_of_limb, P.log_n).bytes;
 }
 
-// sample_poly_uniform of B <= MHE_SAMPLE_MAXB entries into out[e] (the maps checked by the caller,
-// scratch of mhe_internal_uniform_scratch_bytes for at least B entries): the state reset and two launches.
+// sample_poly_uniform of B <= MHE_SAMPLE_MAXB entries into out[e] (scratch of
+// mhe_internal_uniform_scratch_bytes for at least B entries): the state reset and two launches.
 int mhe_internal_uniform_group(mhe_ctx *c, int B, const uint64_t (*seeds)[8], int limbs, const int *prime_of_limb,
                                const int *slot_of_limb, uint64_t *const *out, void *scratch, uint64_t *counters,
                                hipStream_t st)
 {
-    const PrimeDev *primes;
-    const uint64_t *q;
-    int K, log_n;
-    if (mhe_internal_primes(c, &primes, &q, &K, &log_n)) return mhe_internal_fail(MHE_ERR_ARG, "context is not valid");
-    if (B < 1 || B > MHE_SAMPLE_MAXB || !scratch || !counters)
-        return mhe_internal_fail(MHE_ERR_ARG, "invalid sampling arguments");
-    const UniLayout u = uni_layout(c, q, B, limbs, prime_of_limb, log_n);
-    UniB ub{};
+    Primes P;
+    if (int r = primes_of(c, P)) return r;
     LimbMap m;
-    for (int e = 0; e < B; e++)
-    {
-        for (int i = 0; i < 8; i++) ub.s[e].w[i] = seeds[e][i];
-        ub.out[e] = out[e];
-    }
-    for (int l = 0; l < 64; l++)
-    {
-        m.slot[l] = l < limbs ? (signed char)slot_of_limb[l] : -1;
-        m.prime[l] = l < limbs ? prime_of_limb[l] : 0;
-    }
+    if (B < 1 || B > MHE_SAMPLE_MAXB || !scratch || !counters || !limb_map(P.K, limbs, prime_of_limb, slot_of_limb, m))
+        return bad_args();
+    const int log_n = P.log_n;
+    const UniLayout u = uni_layout(c, P.q, B, limbs, prime_of_limb, log_n);
+    UniB ub{ seeds_of(B, seeds), {} };
+    for (int e = 0; e < B; e++) ub.out[e] = out[e];
     u32 *state = static_cast<u32 *>(scratch);
     unsigned char *flags = static_cast<unsigned char *>(scratch) + u.flags_at;
     u64 *val = reinterpret_cast<u64 *>(static_cast<unsigned char *>(scratch) + u.val_at);
     if (hipMemsetAsync(state, 0, 8 * (size_t)MHE_SAMPLE_MAXB, st) != hipSuccess)
         return mhe_internal_fail(MHE_ERR_DEVICE, "sampling state reset failed");
     const u64 blocks = ((u64)limbs << log_n) / 8;
-    hipLaunchKernelGGL(k_uni_bulk, dim3((unsigned)((blocks + 255) / 256), (unsigned)B), dim3(256), 0, st, ub, m, primes,
+    hipLaunchKernelGGL(k_uni_bulk, dim3((unsigned)((blocks + 255) / 256), (unsigned)B), dim3(256), 0, st, ub, m, P.dev,
                        limbs, log_n, flags, u.flag_pitch, state);
-    hipLaunchKernelGGL(k_uni_redraw, dim3((unsigned)B), dim3(256), 0, st, ub, m, primes, limbs, log_n,
+    hipLaunchKernelGGL(k_uni_redraw, dim3((unsigned)B), dim3(256), 0, st, ub, m, P.dev, limbs, log_n,
                        (const unsigned char *)flags, u.flag_pitch, val, (size_t)u.cap, u.cap, state,
                        reinterpret_cast<unsigned long long *>(counters));
     return launch_check("uniform sampling kernel launch failed");
@@ -677,19 +672,15 @@ int mhe_internal_uniform_group(mhe_ctx *c, int B, const uint64_t (*seeds)[8], in
 // The error planes of B symmetric encryptions (keygen.h): small + e * pitch, n signed bytes each.
 int mhe_internal_sk_errors(mhe_ctx *c, int B, const uint64_t (*seeds)[8], signed char *small, size_t pitch, hipStream_t st)
 {
-    const PrimeDev *primes;
-    const uint64_t *q;
-    int K, log_n;
-    if (mhe_internal_primes(c, &primes, &q, &K, &log_n)) return mhe_internal_fail(MHE_ERR_ARG, "context is not valid");
+    Primes P;
+    if (int r = primes_of(c, P)) return r;
+    const int log_n = P.log_n;
     if (!seeds || !small || B < 1 || B > MHE_SAMPLE_MAXB || log_n < 5 || (((uintptr_t)small | pitch) & 3) ||
         (B > 1 && pitch < ((size_t)1 << log_n)))
-        return mhe_internal_fail(MHE_ERR_ARG, "invalid sampling arguments");
-    SeedB sb{};
-    for (int e = 0; e < B; e++)
-        for (int i = 0; i < 8; i++) sb.s[e].w[i] = seeds[e][i];
+        return bad_args();
     const u64 n = (u64)1 << log_n;
-    hipLaunchKernelGGL(k_sk_cbd, dim3((unsigned)((n + kCbdCoeffs - 1) / kCbdCoeffs), (unsigned)B), dim3(256), 0, st, sb,
-                       small, pitch, log_n);
+    hipLaunchKernelGGL(k_sk_cbd, dim3((unsigned)((n + kCbdCoeffs - 1) / kCbdCoeffs), (unsigned)B), dim3(256), 0, st,
+                       seeds_of(B, seeds), small, pitch, log_n);
     return launch_check("sampling kernel launch failed");
 }
 
@@ -697,19 +688,19 @@ MHE_EXPORT int mhe_prng_uniform_batch(mhe_ctx *c, int count, const uint64_t (*se
                                       const int *prime_of_limb, const int *slot_of_limb, uint64_t *const *out,
                                       void *stream)
 {
-    const PrimeDev *primes;
-    const uint64_t *q;
-    int K, log_n;
-    if (mhe_internal_primes(c, &primes, &q, &K, &log_n)) return mhe_internal_fail(MHE_ERR_ARG, "context is not valid");
-    if (count < 1 || !seeds || !out || !uni_maps_ok(K, log_n, limbs, prime_of_limb, slot_of_limb))
-        return mhe_internal_fail(MHE_ERR_ARG, "invalid sampling arguments");
+    Primes P;
+    if (int r = primes_of(c, P)) return r;
+    LimbMap m; // filled again per group
+    if (count < 1 || !seeds || !out || P.log_n < 5 || !limb_map(P.K, limbs, prime_of_limb, slot_of_limb, m))
+        return bad_args();
     for (int i = 0; i < count; i++)
-        if (!out[i]) return mhe_internal_fail(MHE_ERR_ARG, "invalid sampling arguments");
+        if (!out[i]) return bad_args();
     hipStream_t st = (hipStream_t)stream;
     const int Bmax = count < MHE_SAMPLE_MAXB ? count : MHE_SAMPLE_MAXB;
     void *scratch;
     uint64_t *counters;
-    int r = mhe_internal_sample_scratch(c, st, uni_layout(c, q, Bmax, limbs, prime_of_limb, log_n).bytes, &scratch, &counters);
+    int r = mhe_internal_sample_scratch(c, st, uni_layout(c, P.q, Bmax, limbs, prime_of_limb, P.log_n).bytes, &scratch,
+                                        &counters);
     if (r) return r;
     for (int b0 = 0; b0 < count; b0 += MHE_SAMPLE_MAXB)
     {
@@ -725,32 +716,19 @@ MHE_EXPORT int mhe_prng_uniform_bulk(mhe_ctx *c, const uint64_t seed[8], int lim
                                      const int *slot_of_limb, uint64_t *out, uint64_t *rej, uint32_t *rej_count,
                                      uint32_t rej_cap, void *stream)
 {
-    const PrimeDev *primes;
-    const uint64_t *q;
-    int K, log_n;
-    if (mhe_internal_primes(c, &primes, &q, &K, &log_n)) return mhe_internal_fail(MHE_ERR_ARG, "context is not valid");
-    if (!seed || !prime_of_limb || !slot_of_limb || !out || !rej || !rej_count || limbs < 1 || limbs > 64)
-        return mhe_internal_fail(MHE_ERR_ARG, "invalid sampling arguments");
-    Seed s;
+    Primes P;
+    if (int r = primes_of(c, P)) return r;
     LimbMap m;
-    for (int i = 0; i < 8; i++) s.w[i] = seed[i];
-    for (int l = 0; l < 64; l++)
-    {
-        m.slot[l] = l < limbs ? (signed char)slot_of_limb[l] : -1;
-        m.prime[l] = l < limbs ? prime_of_limb[l] : 0;
-        if (l < limbs && (prime_of_limb[l] < 0 || prime_of_limb[l] >= K))
-            return mhe_internal_fail(MHE_ERR_ARG, "invalid sampling arguments");
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const u64 blocks = ((u64)limbs << log_n) / 8;
-    hipLaunchKernelGGL(k_prng_uniform, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, st, s, m, out, primes,
-                       limbs, log_n, rej, rej_count, rej_cap);
+    if (!seed || !out || !rej || !rej_count || !limb_map(P.K, limbs, prime_of_limb, slot_of_limb, m)) return bad_args();
+    const u64 blocks = ((u64)limbs << P.log_n) / 8;
+    hipLaunchKernelGGL(k_prng_uniform, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       seed_of(seed), m, out, P.dev, limbs, P.log_n, rej, rej_count, rej_cap);
     return launch_check("uniform sampling kernel launch failed");
 }
 
 MHE_EXPORT int mhe_prng_apply_fixes(mhe_ctx *c, const uint64_t *fixes_dev, uint32_t count, uint64_t *out, void *stream)
 {
-    if (!c || (count && (!fixes_dev || !out))) return mhe_internal_fail(MHE_ERR_ARG, "invalid sampling arguments");
+    if (!c || (count && (!fixes_dev || !out))) return bad_args();
     if (!count) return MHE_OK;
     hipLaunchKernelGGL(k_prng_apply, dim3((count + 255) / 256), dim3(256), 0, (hipStream_t)stream, fixes_dev, count,
                        out);
@@ -760,29 +738,26 @@ MHE_EXPORT int mhe_prng_apply_fixes(mhe_ctx *c, const uint64_t *fixes_dev, uint3
 MHE_EXPORT int mhe_prng_small(mhe_ctx *c, const uint64_t seed[8], uint64_t byte_offset, int kind, int limbs,
                               uint64_t *out, uint32_t *state_dev, void *stream)
 {
-    const PrimeDev *primes;
-    const uint64_t *q;
-    int K, log_n;
-    if (mhe_internal_primes(c, &primes, &q, &K, &log_n)) return mhe_internal_fail(MHE_ERR_ARG, "context is not valid");
-    if (!seed || !out || limbs < 1 || limbs > K || (byte_offset & 63) || log_n < 5)
-        return mhe_internal_fail(MHE_ERR_ARG, "invalid sampling arguments");
-    Seed s;
-    for (int i = 0; i < 8; i++) s.w[i] = seed[i];
+    Primes P;
+    if (int r = primes_of(c, P)) return r;
+    const int log_n = P.log_n;
+    if (!seed || !out || limbs < 1 || limbs > P.K || (byte_offset & 63) || log_n < 5) return bad_args();
+    const Seed s = seed_of(seed);
     hipStream_t st = (hipStream_t)stream;
     const u64 n = (u64)1 << log_n;
     if (kind == MHE_SAMPLE_TERNARY)
     {
-        if (!state_dev) return mhe_internal_fail(MHE_ERR_ARG, "invalid sampling arguments");
+        if (!state_dev) return bad_args();
         if (hipMemsetAsync(state_dev, 0, 8, st) != hipSuccess)
             return mhe_internal_fail(MHE_ERR_DEVICE, "sampling state reset failed");
         hipLaunchKernelGGL(k_prng_ternary, dim3((unsigned)((n / 16 + 255) / 256), (unsigned)(limbs < 8 ? limbs : 8)),
-                           dim3(256), 0, st, s, byte_offset, out, primes, limbs, log_n, state_dev);
-        hipLaunchKernelGGL(k_prng_ternary_fix, dim3(1), dim3(64), 0, st, s, byte_offset, out, primes, limbs, log_n,
+                           dim3(256), 0, st, s, byte_offset, out, P.dev, limbs, log_n, state_dev);
+        hipLaunchKernelGGL(k_prng_ternary_fix, dim3(1), dim3(64), 0, st, s, byte_offset, out, P.dev, limbs, log_n,
                            state_dev);
     }
     else if (kind == MHE_SAMPLE_CBD)
         hipLaunchKernelGGL(k_prng_cbd, dim3((unsigned)((n + kCbdCoeffs - 1) / kCbdCoeffs), (unsigned)(limbs < 4 ? limbs : 4)),
-                           dim3(256), 0, st, s, byte_offset, (const u32 *)state_dev, out, primes, limbs, log_n);
+                           dim3(256), 0, st, s, byte_offset, (const u32 *)state_dev, out, P.dev, limbs, log_n);
     else
         return mhe_internal_fail(MHE_ERR_ARG, "unknown distribution");
     return launch_check("sampling kernel launch failed");

@@ -646,22 +646,23 @@ public:
     const GaloisKeys &power_of_two_keys();
 
 private:
-    // seeds (optional) receives each digit's public seed (the PRNG seed of its c1)
-    // drawn (optional) receives the digits' bootstrap seeds when the key came from one batched launch
-    // sequence (mhe_encrypt_sk_batch); it stays empty when the per-digit sequence ran
-    void kswitch_key(const std::uint64_t *new_key_dev, PolyStore &dest, std::size_t digits,
-                     std::vector<prng_seed_type> *seeds = nullptr, std::vector<prng_seed_type> *drawn = nullptr);
-    // a key made by the batched path: enough to make it again from its seeds
+    // a key of a create_* call: enough to make it again from its seeds
     struct MadeKey
     {
         std::size_t index;
         std::uint32_t elt; // 0: the relinearization key
         std::size_t digits;
+        // the digits' bootstrap seeds when the key came from one batched launch sequence
+        // (mhe_encrypt_sk_batch); empty when the per-digit sequence ran
         std::vector<prng_seed_type> seeds;
     };
+    // seeds (optional) receives, per key index, each digit's public seed (the PRNG seed of its c1)
+    void make_key(KSwitchKeys &destination, MadeKey m, SeedMap *seeds, std::uint64_t *new_key_dev,
+                  std::vector<MadeKey> &made);
     void redo_if_overflowed(KSwitchKeys &destination, const std::vector<MadeKey> &made);
     void relin_keys_into(RelinKeys &destination, SeedMap *seeds);
-    void galois_keys_into(const std::vector<std::uint32_t> &elts, GaloisKeys &destination, SeedMap *seeds);
+    void galois_keys_into(const std::vector<std::pair<std::uint32_t, std::size_t>> &elt_limbs, GaloisKeys &destination,
+                          SeedMap *seeds);
     SEALContext ctx_;
     SecretKey sk_;
     std::shared_ptr<UniformRandomGeneratorFactory> rng_;

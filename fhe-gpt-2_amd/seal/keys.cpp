@@ -45,22 +45,30 @@ namespace
 // (P mod q_j) * new_key added to limb j of c0; the stored key keeps primes q_0..q_{digits-1} and
 // P ([digits][2][digits+1][n]).  digits = K-1 is SEAL's full key; a truncated key is SEAL's key
 // restricted to those digits and primes.
+//
+// The opening of both ways to make it: the checks, and the store sized and ready to be overwritten.
+std::uint64_t *kswitch_key_store(const SEALContext &ctx, std::size_t digits, PolyStore &dest)
+{
+    const std::size_t K = ctx.key_size(), n = ctx.key_context_data()->parms().poly_modulus_degree();
+    if (K < 2) throw std::logic_error("keyswitching is not supported by the context");
+    if (digits < 1 || digits > K - 1) throw std::invalid_argument("key digits out of range");
+    dest.bind(ctx);
+    dest.resize_words(digits * 2 * (digits + 1) * n, false);
+    return dest.dev_write(ctx.stream(), true);
+}
+
 // The per-digit sequence of general-purpose calls (the whole digit is drawn over the key level, then
 // the kept limbs copied): the path with batched launches off, and the redo of a key whose uniform
 // sampler overflowed its redraw buffer.
 void make_kswitch_key_seq(const SEALContext &ctx, const std::function<prng_seed_type()> &next_seed,
                           const std::uint64_t *sk, const std::uint64_t *new_key, std::size_t digits, PolyStore &dest)
 {
+    std::uint64_t *d = kswitch_key_store(ctx, digits, dest);
     const std::size_t K = ctx.key_size(), n = ctx.key_context_data()->parms().poly_modulus_degree();
     const auto &cm = ctx.key_context_data()->parms().coeff_modulus();
-    if (K < 2) throw std::logic_error("keyswitching is not supported by the context");
-    if (digits < 1 || digits > K - 1) throw std::invalid_argument("key digits out of range");
     mhe_ctx *eng = ctx.engine();
     void *s = ctx.stream();
     const std::size_t KL = digits + 1; // stored limbs
-    dest.bind(ctx);
-    dest.resize_words(digits * 2 * KL * n, false);
-    std::uint64_t *d = dest.dev_write(s, true);
     DevBuf t(eng, s, K * n);
     const bool full = KL == K;
     DevBuf tmp(eng, s, full ? 1 : 2 * K * n);
@@ -93,14 +101,9 @@ void make_kswitch_key(const SEALContext &ctx, const std::function<prng_seed_type
                       std::vector<prng_seed_type> *drawn = nullptr)
 {
     if (!batched_launches() || trace::enabled()) return make_kswitch_key_seq(ctx, next_seed, sk, new_key, digits, dest);
+    std::uint64_t *d = kswitch_key_store(ctx, digits, dest);
     const std::size_t K = ctx.key_size(), n = ctx.key_context_data()->parms().poly_modulus_degree();
-    if (K < 2) throw std::logic_error("keyswitching is not supported by the context");
-    if (digits < 1 || digits > K - 1) throw std::invalid_argument("key digits out of range");
-    void *s = ctx.stream();
     const std::size_t KL = digits + 1; // stored limbs
-    dest.bind(ctx);
-    dest.resize_words(digits * 2 * KL * n, false);
-    std::uint64_t *d = dest.dev_write(s, true);
     std::vector<prng_seed_type> seeds(digits);
     std::vector<const std::uint64_t *> nk(digits, new_key);
     std::vector<int> dg(digits);
@@ -112,8 +115,19 @@ void make_kswitch_key(const SEALContext &ctx, const std::function<prng_seed_type
         outs[j] = d + j * 2 * KL * n;
     }
     chk(mhe_encrypt_sk_batch(ctx.engine(), (int)digits, reinterpret_cast<const std::uint64_t(*)[8]>(seeds.data()), sk,
-                             (int)K, (int)digits, 1, nk.data(), dg.data(), outs.data(), s));
+                             (int)K, (int)digits, 1, nk.data(), dg.data(), outs.data(), ctx.stream()));
     if (drawn) *drawn = std::move(seeds);
+}
+
+// The new key that the key-switching key of Galois element `elt` switches from, over the key level
+// into nk: s(X^elt) (apply_galois_ntt on the NTT-form secret key), or s * s for elt = 0, the
+// relinearization key.
+void new_key_of(const SEALContext &ctx, const std::uint64_t *sk, std::uint32_t elt, std::uint64_t *nk)
+{
+    if (elt)
+        chk(mhe_permute_galois(ctx.engine(), sk, elt, nk, 1, (int)ctx.key_size(), ctx.stream()));
+    else
+        chk(mhe_multiply_plain(ctx.engine(), sk, sk, nk, 1, (int)ctx.key_size(), ctx.stream()));
 }
 
 // A function that hands out `seeds` in order (the replay of a key's draws).
@@ -196,7 +210,7 @@ const std::uint64_t *KSwitchKeys::key_for(std::size_t i, std::size_t L, void *st
                 const std::size_t n = ctx.key_context_data()->parms().poly_modulus_degree();
                 DevBuf rot(ctx.engine(), s, K * n);
                 const std::uint64_t *sk = maker_->sk.dev_read(s);
-                chk(mhe_permute_galois(ctx.engine(), sk, e->second.first, rot.p, 1, (int)K, s));
+                new_key_of(ctx, sk, e->second.first, rot.p);
                 Blake2xbPRNG seeds(e->second.second);
                 PolyStore fresh;
                 std::vector<prng_seed_type> drawn;
@@ -316,22 +330,31 @@ Serializable<PublicKey> KeyGenerator::create_public_key()
     return Serializable<PublicKey>(std::move(pk), SeedMap{ { 0, { seed } } });
 }
 
-void KeyGenerator::kswitch_key(const std::uint64_t *new_key, PolyStore &dest, std::size_t digits,
-                               std::vector<prng_seed_type> *seeds, std::vector<prng_seed_type> *drawn)
+// One key of a create_* call: its new key into nk (K * n words), the key-switching key from this
+// generator's next seeds, inserted at m.index.  A key that came from the batched launches is
+// remembered in `made` with its bootstrap seeds; none is when the per-digit sequence ran.
+void KeyGenerator::make_key(KSwitchKeys &destination, MadeKey m, SeedMap *seeds, std::uint64_t *nk,
+                            std::vector<MadeKey> &made)
 {
+    const std::uint64_t *sk = sk_.data().store().dev_read(ctx_.stream());
+    new_key_of(ctx_, sk, m.elt, nk);
+    std::vector<prng_seed_type> *pub = seeds ? &(*seeds)[m.index] : nullptr;
+    PolyStore key;
     make_kswitch_key(
         ctx_,
         [&] {
             const prng_seed_type sd = rng_->next_seed();
-            if (seeds) seeds->push_back(rnd::stream_prefix_seed(sd));
+            if (pub) pub->push_back(rnd::stream_prefix_seed(sd));
             return sd;
         },
-        sk_.data().store().dev_read(ctx_.stream()), new_key, digits, dest, drawn);
+        sk, nk, m.digits, key, &m.seeds);
+    destination.insert(m.index, std::move(key), m.digits + 1);
+    if (!m.seeds.empty()) made.push_back(std::move(m));
 }
 
 // The end of a create_* call: when the engine reports an overflowed redraw buffer, every key the call
-// made (index, Galois element or 0 for the relinearization key, digits, bootstrap seeds) is made again
-// from its seeds by the per-digit sequence and replaces the batched one.
+// made by the batched path is made again from its seeds by the per-digit sequence and replaces the
+// batched one.
 void KeyGenerator::redo_if_overflowed(KSwitchKeys &destination, const std::vector<MadeKey> &made)
 {
     if (made.empty() || !overflowed(ctx_)) return;
@@ -341,10 +364,7 @@ void KeyGenerator::redo_if_overflowed(KSwitchKeys &destination, const std::vecto
     const std::uint64_t *sk = sk_.data().store().dev_read(s);
     for (const MadeKey &m : made)
     {
-        if (m.elt)
-            chk(mhe_permute_galois(ctx_.engine(), sk, m.elt, nk.p, 1, (int)K, s));
-        else
-            chk(mhe_multiply_plain(ctx_.engine(), sk, sk, nk.p, 1, (int)K, s));
+        new_key_of(ctx_, sk, m.elt, nk.p);
         PolyStore key;
         make_kswitch_key_seq(ctx_, replay(m.seeds), sk, nk.p, m.digits, key);
         destination.insert(m.index, std::move(key), m.digits + 1);
@@ -365,30 +385,42 @@ void KeyGenerator::relin_keys_into(RelinKeys &destination, SeedMap *seeds)
 {
     // create_relin_keys (keygenerator.cpp:115-149): key-switching key of s^2
     const std::size_t K = ctx_.key_size(), n = ctx_.key_context_data()->parms().poly_modulus_degree();
-    void *s = ctx_.stream();
-    DevBuf s2(ctx_.engine(), s, K * n);
-    const std::uint64_t *sk = sk_.data().store().dev_read(s);
-    chk(mhe_multiply_plain(ctx_.engine(), sk, sk, s2.p, 1, (int)K, s));
-    PolyStore key;
-    std::vector<MadeKey> made(1, MadeKey{ RelinKeys::get_index(2), 0, K - 1, {} });
-    kswitch_key(s2.p, key, K - 1, seeds ? &(*seeds)[RelinKeys::get_index(2)] : nullptr, &made[0].seeds);
-    destination.insert(RelinKeys::get_index(2), std::move(key), K);
-    if (made[0].seeds.empty()) made.clear(); // the per-digit sequence ran
+    DevBuf s2(ctx_.engine(), ctx_.stream(), K * n);
+    std::vector<MadeKey> made;
+    make_key(destination, MadeKey{ RelinKeys::get_index(2), 0, K - 1, {} }, seeds, s2.p, made);
     redo_if_overflowed(destination, made);
     destination.parms_id() = ctx_.key_parms_id();
     destination.set_key_limbs(K);
 }
 
+// SEAL's full keys: every element at more limbs than any level has
+static std::vector<std::pair<std::uint32_t, std::size_t>> full_keys(const std::vector<std::uint32_t> &elts)
+{
+    std::vector<std::pair<std::uint32_t, std::size_t>> el;
+    for (std::uint32_t elt : elts) el.emplace_back(elt, ~std::size_t(0));
+    return el;
+}
+
 void KeyGenerator::create_galois_keys(const std::vector<std::pair<std::uint32_t, std::size_t>> &elt_limbs,
                                       GaloisKeys &destination)
 {
-    // create_galois_keys (keygenerator.cpp:152-190): per element, the key-switching key of
-    // s(X^elt) (apply_galois_ntt on the NTT-form secret key); here truncated per element to the
-    // level it is used at (limbs = ciphertext limbs; >= K-1 keeps SEAL's full key)
+    galois_keys_into(elt_limbs, destination, nullptr);
+}
+
+void KeyGenerator::create_galois_keys_from_elts(const std::vector<std::uint32_t> &elts, GaloisKeys &destination)
+{
+    galois_keys_into(full_keys(elts), destination, nullptr);
+}
+
+void KeyGenerator::galois_keys_into(const std::vector<std::pair<std::uint32_t, std::size_t>> &elt_limbs,
+                                    GaloisKeys &destination, SeedMap *seeds)
+{
+    // create_galois_keys (keygenerator.cpp:152-190): per element, the key-switching key of s(X^elt),
+    // here truncated per element to the level it is used at (limbs = ciphertext limbs; >= K-1 keeps
+    // SEAL's full key); seeds receives every digit's public seed per key index
     const std::size_t K = ctx_.key_size(), n = ctx_.key_context_data()->parms().poly_modulus_degree();
     if (K < 2) throw std::logic_error("keyswitching is not supported by the context");
-    void *s = ctx_.stream();
-    DevBuf rot(ctx_.engine(), s, K * n);
+    DevBuf rot(ctx_.engine(), ctx_.stream(), K * n);
     std::vector<MadeKey> made;
     for (const auto &el : elt_limbs)
     {
@@ -396,44 +428,7 @@ void KeyGenerator::create_galois_keys(const std::vector<std::pair<std::uint32_t,
         if (!(elt & 1) || elt >= 2 * n) throw std::invalid_argument("Galois element is not valid");
         if (destination.has_key(elt)) continue;
         const std::size_t digits = std::min(K - 1, std::max<std::size_t>(el.second, 1));
-        const std::uint64_t *sk = sk_.data().store().dev_read(s);
-        chk(mhe_permute_galois(ctx_.engine(), sk, elt, rot.p, 1, (int)K, s));
-        PolyStore key;
-        MadeKey m{ GaloisKeys::get_index(elt), elt, digits, {} };
-        kswitch_key(rot.p, key, digits, nullptr, &m.seeds);
-        destination.insert(m.index, std::move(key), digits + 1);
-        if (!m.seeds.empty()) made.push_back(std::move(m));
-    }
-    redo_if_overflowed(destination, made);
-    destination.parms_id() = ctx_.key_parms_id();
-    destination.set_key_limbs(K);
-}
-
-void KeyGenerator::create_galois_keys_from_elts(const std::vector<std::uint32_t> &elts, GaloisKeys &destination)
-{
-    galois_keys_into(elts, destination, nullptr);
-}
-
-void KeyGenerator::galois_keys_into(const std::vector<std::uint32_t> &elts, GaloisKeys &destination, SeedMap *seeds)
-{
-    // create_galois_keys (keygenerator.cpp:152-190) with SEAL's full keys; seeds receives every
-    // digit's public seed per key index
-    const std::size_t K = ctx_.key_size(), n = ctx_.key_context_data()->parms().poly_modulus_degree();
-    if (K < 2) throw std::logic_error("keyswitching is not supported by the context");
-    void *s = ctx_.stream();
-    DevBuf rot(ctx_.engine(), s, K * n);
-    std::vector<MadeKey> made;
-    for (std::uint32_t elt : elts)
-    {
-        if (!(elt & 1) || elt >= 2 * n) throw std::invalid_argument("Galois element is not valid");
-        if (destination.has_key(elt)) continue;
-        const std::uint64_t *sk = sk_.data().store().dev_read(s);
-        chk(mhe_permute_galois(ctx_.engine(), sk, elt, rot.p, 1, (int)K, s));
-        PolyStore key;
-        MadeKey m{ GaloisKeys::get_index(elt), elt, K - 1, {} };
-        kswitch_key(rot.p, key, K - 1, seeds ? &(*seeds)[m.index] : nullptr, &m.seeds);
-        destination.insert(m.index, std::move(key), K);
-        if (!m.seeds.empty()) made.push_back(std::move(m));
+        make_key(destination, MadeKey{ GaloisKeys::get_index(elt), elt, digits, {} }, seeds, rot.p, made);
     }
     redo_if_overflowed(destination, made);
     destination.parms_id() = ctx_.key_parms_id();
@@ -513,7 +508,7 @@ Serializable<GaloisKeys> KeyGenerator::create_galois_keys(const std::vector<int>
 {
     GaloisKeys gk;
     SeedMap seeds;
-    galois_keys_into(elts_from_steps(ctx_, steps), gk, &seeds);
+    galois_keys_into(full_keys(elts_from_steps(ctx_, steps)), gk, &seeds);
     return Serializable<GaloisKeys>(std::move(gk), std::move(seeds));
 }
 
@@ -521,7 +516,7 @@ Serializable<GaloisKeys> KeyGenerator::create_galois_keys()
 {
     GaloisKeys gk;
     SeedMap seeds;
-    galois_keys_into(elts_all(ctx_), gk, &seeds);
+    galois_keys_into(full_keys(elts_all(ctx_)), gk, &seeds);
     return Serializable<GaloisKeys>(std::move(gk), std::move(seeds));
 }
 

@@ -120,3 +120,44 @@ def test_ternary_redraw_path():
     e0, _ = eng.prng_small("cbd", 3, seed, 4 * n, state=state)
     raw = O.prng_bytes(seed, 4 * n + extra + 6 * n)[4 * n + extra:]
     assert np.array_equal(mhe.Engine.to_host(e0), _small_from_stream("cbd", raw, n, moduli, 3))
+
+
+@pytest.fixture(scope="module")
+def ten_limbs():
+    """Ten primes at the smallest ring: more limbs than the y extent of the single-seed kernels' grids
+    (8 for ternary, 4 for CBD), so a workgroup's limb-stride loop writes more than one limb."""
+    log_n = 12
+    moduli = _heavy_reject_primes(log_n, 10)
+    return mhe.Engine(log_n, moduli, device=0), O.Context(log_n, moduli), moduli
+
+
+@pytest.mark.gpu
+def test_small_samplers_limb_stride(ten_limbs):
+    eng, oc, moduli = ten_limbs
+    n = eng.n
+    u, state = eng.prng_small("ternary", 10, SEED, 0)
+    assert state.cpu().tolist() == [0, 0]
+    e, _ = eng.prng_small("cbd", 10, SEED, 4 * n)
+    raw = O.prng_bytes(SEED, 10 * n)
+    assert np.array_equal(mhe.Engine.to_host(u), _small_from_stream("ternary", raw, n, moduli, 10))
+    assert np.array_equal(mhe.Engine.to_host(e), _small_from_stream("cbd", raw[4 * n:], n, moduli, 10))
+
+
+@pytest.mark.gpu
+def test_ternary_redraw_limb_stride(ten_limbs):
+    """test_ternary_redraw_path over ten limbs: the sequential fix writes every limb."""
+    import json
+    import os
+
+    fx = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "ternary_redraw_seed.json")))
+    seed = [fx["seed0"], 2, 3, 4, 5, 6, 7, 8]
+    eng, oc, moduli = ten_limbs
+    n = eng.n
+    assert fx["log_n"] == 12
+    u, state = eng.prng_small("ternary", 10, seed, 0)
+    assert np.array_equal(mhe.Engine.to_host(u), oc.sample(seed, "ternary", 10))
+    extra = int(state[0].item())
+    assert extra >= 4 and extra % 4 == 0
+    e0, _ = eng.prng_small("cbd", 10, seed, 4 * n, state=state)
+    raw = O.prng_bytes(seed, 4 * n + extra + 6 * n)[4 * n + extra:]
+    assert np.array_equal(mhe.Engine.to_host(e0), _small_from_stream("cbd", raw, n, moduli, 10))
